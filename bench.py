@@ -9,8 +9,21 @@ A "step" is one pass of the hot path (train_generator.py:170-290: Phase C + Phas
 updates, and for N > 1 both gradient all-reduces) over one synthetic CIFAR-10-shaped batch of 128
 images per GPU that is already resident in HBM.  `--gpus N` without a torchrun environment starts the
 N ranks itself (a child `python -m torch.distributed.run ...`, spawned before anything touches the GPU).
-Prints ONE JSON line on rank 0 (contract in the task statement): whole-job images/sec, plus
+Prints ONE JSON line on rank 0: whole-job images/sec and ms_per_step of the K timed steps.  A plain run
+does only that (set-up, W warm-up steps, K timed steps, the line).
 
+  --dump-outputs DIR
+                after the timed steps, what they computed as of the last one (dump_outputs) as DIR/<name>.npy;
+                the same arguments give the same inputs (batches, initial weights, host-drawn randomness) and,
+                the step running in the library's deterministic mode, the same outputs.
+  --full        everything else the benchmark measures or checks, in the same line (each part can be
+                dropped with its --no-* option):
+
+  golden_gate   before anything is timed the first two steps at B = 128 (augmentation off, recorded num_bd /
+                sigma) are checked against tests/golden/step_b128.npz -- losses recorded from the reference's own
+                modules on the same batches and seeds -- and the run aborts on a mismatch;
+  host_enqueue_ms_per_step
+                the host's cost of enqueueing one step, with the device parked behind a spin kernel;
   roofline      the dominant kernel (the convolution kernel family with the most device time):
                 algorithmic FLOPs of its launches / their HIP-event durations, measured in a second,
                 instrumented replay of the same K steps (events on the launch stream), against the
@@ -21,10 +34,6 @@ Prints ONE JSON line on rank 0 (contract in the task statement): whole-job image
   pytorch_rocm_baseline
                 the same restatement run by stock PyTorch-ROCm on this GPU (ATen + MIOpen), fp32 and bf16
                 autocast: BASELINE.json configs[1]'s "vs PyTorch-ROCm baseline" row.
-
-Before anything is timed the first two steps at B = 128 (augmentation off, recorded num_bd / sigma) are
-checked against tests/golden/step_b128.npz -- losses recorded from the reference's own modules on the same
-batches and seeds -- and the run aborts on a mismatch: the number is for a shape whose results are checked.
 """
 import argparse
 import json
@@ -380,6 +389,37 @@ def pytorch_rocm_baseline(device, steps=10, budget_s=90.0):
     return out
 
 
+# --------------------------------------------------------------------------------------------- outputs
+
+
+DUMP_SAMPLE = 1 << 18     # elements kept of a larger state tensor (the whole state is ~80 MB): a fixed, seeded sample
+
+
+def dump_outputs(path, st, netc, netg, metrics):
+    """What a caller of the timed step holds after its last step, as DIR/<name>.npy (float32; float64 for the
+    logged sums and the BatchNorm step counters): netC.<key> / netG.<key>, the surrogate's and the generator's
+    state_dict after both SGD updates; inputs_bd, the generator-triggered batch of Phase G; metric.<key>, the
+    running sums of read_metrics().  Arrays keep their logical shape and order (independent of the engines'
+    storage layouts); a state tensor of more than DUMP_SAMPLE elements is flattened and cut to the same seeded index
+    sample in every run.  The step runs in deterministic mode (main), so two runs with the same arguments write the
+    same bits."""
+    os.makedirs(path, exist_ok=True)
+    arrays = [("inputs_bd", st.bd, False)]
+    for tag, m in (("netC", netc), ("netG", netg)):
+        arrays += [("%s.%s" % (tag, k), v, True) for k, v in m.state_dict().items()]
+    arrays += [("metric." + k, torch.tensor(float(v), dtype=torch.float64), False) for k, v in metrics.items()]
+    total = 0
+    for name, v, sample in arrays:
+        v = v.detach()
+        if sample and v.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            v = v.flatten()[idx.to(v.device)]
+        a = (v.double() if v.dtype in (torch.float64, torch.int64) else v.float()).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    log("outputs of the last step: %d arrays, %.1f MB -> %s" % (len(arrays), total / 1e6, path))
+
+
 # --------------------------------------------------------------------------------------------- main
 
 
@@ -400,6 +440,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also the golden gate, host-enqueue probe, instrumented roofline replay and the PyTorch-ROCm / "
+                         "CPU baselines (each can be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed, as of its last step, to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-torch-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -408,6 +453,10 @@ def main():
                     help="cifar10 = BASELINE configs[1] (the metric's configuration); celeba = configs[3]'s shape "
                          "(64 x 64, 8 classes, ResNet18), informational")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_torch_baseline = args.no_roofline = args.no_golden_gate = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -426,6 +475,11 @@ def main():
     local_rank = local_rank if backend == "nccl" else local_rank % torch.cuda.device_count()
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
+    # the library's deterministic mode (ordered weight-gradient reductions instead of fp32 atomics): the same arguments
+    # give the same results in every run; with atomics, rounding-level differences in one step grow into different
+    # parameters over a run.  COMBAT_DETERMINISTIC=0 times the atomics form.
+    from combat_amd import engine
+    engine.set_deterministic(os.environ.get("COMBAT_DETERMINISTIC", "1") != "0")
     pg = None
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -484,6 +538,10 @@ def main():
         elapsed = float(tt)
     log("timed region: %.3f s (%.3f ms/step; host thread inside run() %.3f ms/step -- it runs ahead of the device until the "
         "hardware queues fill and then moves at the device's pace)" % (elapsed, elapsed / args.steps * 1e3, host_s / args.steps * 1e3))
+    metrics = st.read_metrics()
+    finite = all(np.isfinite(v) for v in metrics.values())
+    if args.dump_outputs and rank == 0:      # before anything below runs the step again
+        dump_outputs(args.dump_outputs, st, netc, netg, metrics)
     # the host's own cost of enqueueing a step: the device is parked behind a spin kernel, so no call waits for queue space
     # (three steps = ~2 100 queue packets fit); outside the timed region
     host_ms = None
@@ -497,8 +555,6 @@ def main():
         torch.cuda.synchronize()
         log("host enqueue %.3f ms/step (device parked: the cost of the %s replay + the step's own host work)" % (
             host_ms, "C (combat_plan_run)" if os.environ.get("COMBAT_PLAN_PY", "0") != "1" else "Python"))
-    metrics = st.read_metrics()
-    finite = all(np.isfinite(v) for v in metrics.values())
 
     roof = None
     if not args.no_roofline:
@@ -538,6 +594,7 @@ def main():
                        "per_gpu_batch": opt.bs, "global_batch": opt.bs * world,
                        "parallelism": "dp%d (RCCL all-reduce of netC grads in Phase C, netG grads in Phase G)" % world,
                        "gflop_per_image_algorithmic": 11.67, "losses_finite": finite,
+                       "deterministic": engine.deterministic(),
                        "golden_gate": gate, "host_enqueue_ms_per_step": None if host_ms is None else round(host_ms, 3)},
             "roofline": roof,
         }

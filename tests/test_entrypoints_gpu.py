@@ -230,12 +230,12 @@ def test_c_abi_allreduce_world1():
 
 def test_bench_spawns_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` outside torchrun starts 2 ranks itself (child torch.distributed.run, gloo
-    rehearsal on this one GPU) and rank 0 prints n_gpus = 2."""
+    rehearsal on this one GPU) and rank 0 prints n_gpus = 2; with --full, after the golden gate."""
     import json
     env = dict(os.environ, PYTHONPATH=ROOT, COMBAT_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-torch-baseline", "--no-roofline"], env=env, capture_output=True, text=True,
                        timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-3000:]
@@ -243,3 +243,47 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     out = json.loads(line)
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 256 and out["value"] > 0
     assert out["config"]["golden_gate"]["ok"]
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and leaves the --full parts out of its line; with
+    --dump-outputs it writes the last step's state as float32 / float64 arrays, 64 MB at most, all finite, and a
+    second run with the same arguments writes the same bits (the step runs in deterministic mode)."""
+    import json
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "COMBAT_DETERMINISTIC"):
+        env.pop(k, None)
+    dumps = []
+    for run_i in range(2):
+        out_dir = tmp_path / ("out%d" % run_i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(out_dir)], env=env, capture_output=True, text=True, timeout=600,
+                           cwd=str(tmp_path))
+        assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 3 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["unit"] == "images/sec" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+        assert out["roofline"] is None and out["config"]["golden_gate"] is None and out["config"]["losses_finite"]
+        assert out["config"]["deterministic"] is True
+        assert "cpu_baseline" not in out and "pytorch_rocm_baseline" not in out
+        dumps.append({f: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))})
+    a, b = dumps
+    assert "inputs_bd.npy" in a and "metric.loss_c_sum.npy" in a and "netC.linear.weight.npy" in a
+    assert any(f.startswith("netG.") for f in a)
+    for f, x in a.items():
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), f
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["inputs_bd.npy"].shape == (128, 3, 32, 32)
+    # the running sums cover every step run before the dump: 2 warm-up + 3 timed steps of 128 images
+    assert float(a["metric.samples.npy"]) == 128 * 5
+    # the dump is the trained state, not the initial one: bench.py's seeded initial weights have moved
+    import bench
+    netc0, netg0, _, _ = bench.build_nets("cpu")
+    for tag, net in (("netC", netc0), ("netG", netg0)):
+        for k, v in net.state_dict().items():
+            if k.endswith("weight") and v.numel() <= bench.DUMP_SAMPLE:
+                assert not np.array_equal(a["%s.%s.npy" % (tag, k)], v.numpy()), (tag, k)
+    assert sorted(a) == sorted(b)
+    differ = [f for f in a if not np.array_equal(a[f], b[f])]
+    assert not differ, differ
