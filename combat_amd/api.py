@@ -16,16 +16,23 @@ def _c(hw: int, ratio: float, device):
     return _consts[key]
 
 
-def create_backdoor(netG, inputs: torch.Tensor, opt, sigma: float = None) -> torch.Tensor:
+def create_backdoor(netG, inputs: torch.Tensor, opt, sigma: float = None, noise_from: torch.Tensor = None) -> torch.Tensor:
     """netG -> low_freq -> clamp(x + noise*rate) -> GaussianBlur (one sigma per call, drawn here from
-    torch's global generator like T.GaussianBlur) for a float32 NCHW device batch; no gradient."""
+    torch's global generator like T.GaussianBlur) for a float32 NCHW device batch; no gradient.
+    noise_from: a batch of the same shape whose generator noise is mixed onto `inputs` instead of their own -- the
+    input-aware attack's cross images (train_generator_inputaware.py:236-238, 412-414)."""
     n, _, hw, _ = inputs.shape
+    if noise_from is not None and tuple(noise_from.shape) != tuple(inputs.shape):
+        raise ValueError("create_backdoor: noise_from %s must have the shape of inputs %s"
+                         % (tuple(noise_from.shape), tuple(inputs.shape)))
     if n == 0:
         return inputs
     eng = netG._net_engine()
     eng.refresh()
     inputs = inputs.contiguous().float()
     if netG.arch == "gridgen":   # WaNet: warp by the generator's field (train_generator_wanet.py:151-157, :346-352)
+        if noise_from is not None:
+            raise ValueError("create_backdoor: noise_from needs a noise generator (the warping trigger has no per-image noise)")
         from ._lib import lib
         g = eng.forward_grid(hw, float(opt.grid_rescale))
         out = torch.empty_like(inputs)
@@ -34,7 +41,7 @@ def create_backdoor(netG, inputs: torch.Tensor, opt, sigma: float = None) -> tor
         return out
     from .engine import pad_batch
     slot = eng.slot("api", pad_batch(n), hw)
-    ops.image_to_c8(inputs, eng.input(slot))
+    ops.image_to_c8(inputs if noise_from is None else noise_from.contiguous().float(), eng.input(slot))
     eng.forward_plan(slot).run()
     if sigma is None:
         sigma = trigger.sample_sigma(getattr(opt, "sigma", (0.1, 1.0)))

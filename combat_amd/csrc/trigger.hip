@@ -84,22 +84,20 @@ __device__ __forceinline__ void store_hilo(__bf16 *px8, int c, float v) {   // h
 
 // One workgroup per (channel, image): 3n workgroups.  LDS (floats): Pl [hw][hw+1], Pr [hw][hw], A [hw][hw],
 // B [hw][hw+1].  P is symmetric (D^T diag(mask) D), so P N P^T = (P N) P needs no transposed operand.
-__global__ __launch_bounds__(256) void trigger_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
-                                                          const float *__restrict__ P, const float *__restrict__ k1,
-                                                          float rate, int hw, const int *__restrict__ src_index,
-                                                          float *__restrict__ out,
-                                                          __bf16 *__restrict__ out_c8, float *__restrict__ mse) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int hw2 = hw * hw, lp = hw + 1, tid = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
-    const long src = src_index ? src_index[img] : img;   // row of x / noise this output image is made from
+// The per-(channel, image) body, shared by trigger_fwd_kernel and trigger_pair_fwd_kernel: xi is the image's plane
+// of channel c, nz its noise pixels (c8), outp its output plane (the image's row `img` of out_c8 / mse).
+__device__ __forceinline__ void trigger_fwd_plane(float *sm, const float *__restrict__ xi, const __bf16 *__restrict__ nz,
+                                                  const float *__restrict__ P, const float *__restrict__ k1, float rate,
+                                                  int hw, int c, long img, float *__restrict__ outp,
+                                                  __bf16 *__restrict__ out_c8, float *__restrict__ mse) {
+    const int hw2 = hw * hw, lp = hw + 1, tid = threadIdx.x;
     float *Pl = sm, *Pr = Pl + hw * lp, *A = Pr + hw2, *B = A + hw2;
     const float kk[3] = {k1[0], k1[1], k1[2]};
-    const float *xi = x + (src * 3 + c) * hw2;
     for (int o = tid; o < hw2; o += 256) {
         const float pv = P[o];
         Pr[o] = pv;
         Pl[(o / hw) * lp + (o % hw)] = pv;
-        A[o] = (float)noise[(src * hw2 + o) * 8 + c];
+        A[o] = (float)nz[(long)o * 8 + c];
     }
     __syncthreads();
     mm4(Pl, lp, A, B, lp, hw, tid);            // B = P N
@@ -115,10 +113,10 @@ __global__ __launch_bounds__(256) void trigger_fwd_kernel(const float *__restric
     float se = 0.f;
     for (int o = tid; o < hw2; o += 256) {
         const float v = A[o];
-        out[((long)img * 3 + c) * hw2 + o] = v;
+        outp[o] = v;
         const float d = v - xi[o];
         se = fmaf(d, d, se);
-        if (out_c8) store_hilo(out_c8 + ((long)img * hw2 + o) * 8, c, v);
+        if (out_c8) store_hilo(out_c8 + (img * hw2 + o) * 8, c, v);
     }
     if (mse) {
         __syncthreads();
@@ -132,28 +130,53 @@ __global__ __launch_bounds__(256) void trigger_fwd_kernel(const float *__restric
     }
 }
 
+__global__ __launch_bounds__(256) void trigger_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                          const float *__restrict__ P, const float *__restrict__ k1,
+                                                          float rate, int hw, const int *__restrict__ src_index,
+                                                          float *__restrict__ out,
+                                                          __bf16 *__restrict__ out_c8, float *__restrict__ mse) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.x, img = blockIdx.y;
+    const long src = src_index ? src_index[img] : img;   // row of x / noise this output image is made from
+    trigger_fwd_plane(sm, x + (src * 3 + c) * hw2, noise + src * hw2 * 8, P, k1, rate, hw, c, img,
+                      out + ((long)img * 3 + c) * hw2, out_c8, mse);
+}
+
+// The paired trigger of the input-aware step: 2n workgroup rows over ONE batch of images x [n] and the generator's
+// output for 2n images.  Row i < n: out_bd[i] = T(x[i], noise[i], k1[0]) with its squared-error partials; row n + i:
+// out_cross[i] = T(x[i], noise[n + i], k1[1]) (the noise of another image on x[i]).  Per image the same body as
+// trigger_fwd_kernel, so the results are those of two calls of it.
+__global__ __launch_bounds__(256) void trigger_pair_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                               const float *__restrict__ P, const float *__restrict__ k1,
+                                                               float rate, int n, int hw, float *__restrict__ out_bd,
+                                                               float *__restrict__ out_cross, float *__restrict__ mse) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.x, row = blockIdx.y;
+    const int cross = row >= n, img = cross ? row - n : row;
+    trigger_fwd_plane(sm, x + ((long)img * 3 + c) * hw2, noise + (long)row * hw2 * 8, P, k1 + 3 * cross, rate, hw, c,
+                      img, (cross ? out_cross : out_bd) + ((long)img * 3 + c) * hw2, nullptr, cross ? nullptr : mse);
+}
+
 // d_noise = rate * P * ( clampmask .* (Kb^T * (d_out + 2*l2*(out-x)) * Kb) ) * P      (P symmetric)
 // LDS (floats): Pl, Pr, A, B as above + G [hw][hw]
-__global__ __launch_bounds__(256) void trigger_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
-                                                          const float *__restrict__ P, const float *__restrict__ k1,
-                                                          float rate, int hw, const float *__restrict__ d_out,
-                                                          const float *__restrict__ d_out2,
-                                                          const float *__restrict__ outp, float l2_scale,
-                                                          int pre_tanh, __bf16 *__restrict__ d_noise) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int hw2 = hw * hw, lp = hw + 1, tid = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
+// The per-(channel, image) body, shared by trigger_bwd_kernel and trigger_pair_bwd_kernel: xi / nz / dn are the
+// image's plane of x, noise pixels and gradient pixels (c8); d_out, d_out2, outp point at its plane of channel c.
+__device__ __forceinline__ void trigger_bwd_plane(float *sm, const float *__restrict__ xi, const __bf16 *__restrict__ nz,
+                                                  const float *__restrict__ P, const float *__restrict__ k1, float rate,
+                                                  int hw, int c, const float *__restrict__ d_out,
+                                                  const float *__restrict__ d_out2, const float *__restrict__ outp,
+                                                  float l2_scale, int pre_tanh, __bf16 *__restrict__ dn) {
+    const int hw2 = hw * hw, lp = hw + 1, tid = threadIdx.x;
     float *Pl = sm, *Pr = Pl + hw * lp, *A = Pr + hw2, *B = A + hw2, *G = B + hw * lp;
     const float kk[3] = {k1[0], k1[1], k1[2]};
-    const float *xi = x + ((long)img * 3 + c) * hw2;
     for (int o = tid; o < hw2; o += 256) {
         const float pv = P[o];
         Pr[o] = pv;
         Pl[(o / hw) * lp + (o % hw)] = pv;
-        A[o] = (float)noise[((long)img * hw2 + o) * 8 + c];
-        const long go = ((long)img * 3 + c) * hw2 + o;
-        float g = d_out ? d_out[go] : 0.f;
-        if (d_out2) g += d_out2[go];      // a second gradient of the same tensor (another classifier's share)
-        if (l2_scale != 0.f) g = fmaf(2.f * l2_scale, outp[go] - xi[o], g);
+        A[o] = (float)nz[(long)o * 8 + c];
+        float g = d_out ? d_out[o] : 0.f;
+        if (d_out2) g += d_out2[o];      // a second gradient of the same tensor (another classifier's share)
+        if (l2_scale != 0.f) g = fmaf(2.f * l2_scale, outp[o] - xi[o], g);
         G[o] = g;
     }
     __syncthreads();
@@ -175,10 +198,10 @@ __global__ __launch_bounds__(256) void trigger_bwd_kernel(const float *__restric
     mm4(B, lp, Pr, A, hw, hw, tid);              // A = P g P
     __syncthreads();
     for (int o = tid; o < hw2; o += 256) {
-        __bf16 *px = d_noise + ((long)img * hw2 + o) * 8;
+        __bf16 *px = dn + (long)o * 8;
         float r = A[o];
         if (pre_tanh) {  // noise = tanh(z): hand back the gradient w.r.t. z
-            const float t = (float)noise[((long)img * hw2 + o) * 8 + c];
+            const float t = (float)nz[(long)o * 8 + c];
             r *= 1.f - t * t;
         }
         px[c] = (__bf16)r;
@@ -187,6 +210,40 @@ __global__ __launch_bounds__(256) void trigger_bwd_kernel(const float *__restric
             *reinterpret_cast<uint2 *>(px + 4) = make_uint2(0u, 0u);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void trigger_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                          const float *__restrict__ P, const float *__restrict__ k1,
+                                                          float rate, int hw, const float *__restrict__ d_out,
+                                                          const float *__restrict__ d_out2,
+                                                          const float *__restrict__ outp, float l2_scale,
+                                                          int pre_tanh, __bf16 *__restrict__ d_noise) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.x, img = blockIdx.y;
+    const long pl = ((long)img * 3 + c) * hw2;
+    trigger_bwd_plane(sm, x + pl, noise + (long)img * hw2 * 8, P, k1, rate, hw, c, d_out ? d_out + pl : nullptr,
+                      d_out2 ? d_out2 + pl : nullptr, outp ? outp + pl : nullptr, l2_scale, pre_tanh,
+                      d_noise + (long)img * hw2 * 8);
+}
+
+// Backward of trigger_pair_fwd_kernel, one launch over 2n workgroup rows.  Row i < n: the gradient of noise[i] from
+// d_bd (+ d_bd2) and the L2 term on out_bd, blur k1[0]; row n + i: the gradient of noise[n + i] from d_cross alone
+// (no L2 term), blur k1[1].  Per image the same body as trigger_bwd_kernel.
+__global__ __launch_bounds__(256) void trigger_pair_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                               const float *__restrict__ P, const float *__restrict__ k1,
+                                                               float rate, int n, int hw, const float *__restrict__ d_bd,
+                                                               const float *__restrict__ d_bd2,
+                                                               const float *__restrict__ out_bd, float l2_scale,
+                                                               const float *__restrict__ d_cross, int pre_tanh,
+                                                               __bf16 *__restrict__ d_noise) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.x, row = blockIdx.y;
+    const int cross = row >= n, img = cross ? row - n : row;
+    const long pl = ((long)img * 3 + c) * hw2;
+    const float *g1 = cross ? d_cross : d_bd, *g2 = cross ? nullptr : d_bd2;
+    trigger_bwd_plane(sm, x + pl, noise + (long)row * hw2 * 8, P, k1 + 3 * cross, rate, hw, c, g1 ? g1 + pl : nullptr,
+                      g2 ? g2 + pl : nullptr, cross || !out_bd ? nullptr : out_bd + pl, cross ? 0.f : l2_scale, pre_tanh,
+                      d_noise + (long)row * hw2 * 8);
 }
 
 // ------------------------------------------------------------------ augmentation
@@ -480,6 +537,38 @@ extern "C" int combat_trigger_bwd(const float *x, const void *noise, const float
     COMBAT_LAUNCH(trigger_bwd_kernel, dim3(3, n), dim3(256), bytes, as_stream(stream), x,
                        reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, d_out, d_out2, out, l2_scale,
                        pre_tanh, reinterpret_cast<__bf16 *>(d_noise));
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+
+extern "C" int combat_trigger_pair_fwd(const float *x, const void *noise, const float *P, const float *k1,
+                                       float noise_rate, int32_t n, int32_t hw, float *out_bd, float *out_cross,
+                                       float *mse_partial, void *stream) {
+    COMBAT_PLAN_HOOK(combat_trigger_pair_fwd, x, noise, P, k1, noise_rate, n, hw, out_bd, out_cross, mse_partial);
+    if (!x || !noise || !P || !k1 || !out_bd || !out_cross || n < 0 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (n == 0) return COMBAT_OK;
+    const int bytes = (4 * hw * hw + 2 * hw) * 4;
+    if (set_smem(trigger_pair_fwd_kernel, bytes)) return COMBAT_ELAUNCH;
+    COMBAT_LAUNCH(trigger_pair_fwd_kernel, dim3(3, 2 * n), dim3(256), bytes, as_stream(stream), x,
+                       reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, n, hw, out_bd, out_cross, mse_partial);
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+
+extern "C" int combat_trigger_pair_bwd(const float *x, const void *noise, const float *P, const float *k1,
+                                       float noise_rate, int32_t n, int32_t hw, const float *d_bd, const float *d_bd2,
+                                       const float *out_bd, float l2_scale, const float *d_cross, int32_t pre_tanh,
+                                       void *d_noise, void *stream) {
+    COMBAT_PLAN_HOOK(combat_trigger_pair_bwd, x, noise, P, k1, noise_rate, n, hw, d_bd, d_bd2, out_bd, l2_scale, d_cross,
+                     pre_tanh, d_noise);
+    if (!x || !noise || !P || !k1 || !d_noise || n < 0 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (l2_scale != 0.f && !out_bd) return COMBAT_EINVAL;
+    if (n == 0) return COMBAT_OK;
+    const int bytes = (5 * hw * hw + 2 * hw) * 4;
+    if (set_smem(trigger_pair_bwd_kernel, bytes)) return COMBAT_ELAUNCH;
+    COMBAT_LAUNCH(trigger_pair_bwd_kernel, dim3(3, 2 * n), dim3(256), bytes, as_stream(stream), x,
+                       reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, n, hw, d_bd, d_bd2, out_bd, l2_scale,
+                       d_cross, pre_tanh, reinterpret_cast<__bf16 *>(d_noise));
     CB_LAUNCH_CHECK();
     return COMBAT_OK;
 }

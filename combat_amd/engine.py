@@ -288,6 +288,24 @@ _AUX_STREAMS: Dict = {}
 _AUX_POINTERS: Dict = {}
 
 
+class PlanSeq:
+    """Plans run one after the other as one pass (the two halves of a two_loss pass)."""
+
+    def __init__(self, name: str, plans):
+        self.name, self.plans = name, list(plans)
+
+    @property
+    def calls(self):
+        return [c for p in self.plans for c in p.calls]
+
+    def run(self, prof: Optional[list] = None, on_mark=None) -> None:
+        for p in self.plans:
+            p.run(prof, on_mark=on_mark)
+
+    def __len__(self):
+        return sum(len(p) for p in self.plans)
+
+
 def _aux_pointers(parent: torch.cuda.Stream, n: int):
     """void*[n] of the parent stream's auxiliary streams, for combat_plan_run (built once per parent stream)."""
     key = (parent.device, parent.cuda_stream, n)
@@ -944,12 +962,27 @@ class PreActEngine(NetEngine):
         "b%d.%s" % (b, s) for b in range(8) for s in ("y1", "out", "sc", "a1", "act")) + ("stem.act",)
 
     def forward_plan(self, slot: Slot, train: bool, loss_weight: float = 1.0, with_targets2: bool = False,
-                     split_head: bool = False, head_bwd: bool = False) -> Plan:
+                     split_head: bool = False, head_bwd: bool = False, two_loss: bool = False) -> Plan:
         """split_head (eval only): the batch is two independent halves [metric-only images ; images whose
         loss is differentiated]; the head runs once per half with separate loss / counter cells
         (first half -> correct[0] of slot 'loss0/correct0' cells, second half -> the usual ones).
         head_bwd: the head launch also produces dlogits and the gradient w.r.t. the feature map ('g.feat':
-        combat_head_fwd_bwd), for a pass whose backward plan (built with head_done=True) follows at once."""
+        combat_head_fwd_bwd), for a pass whose backward plan (built with head_done=True) follows at once.
+        two_loss (eval only): the batch is two halves whose losses are BOTH differentiated (the input-aware step's
+        [aug(bd) ; aug(bd2)], labels targets[:n] / targets[n:]): first half -> the usual cells, second half ->
+        'loss1' / 'correct1'; the matching backward is backward_eval_plan(half_weights=...).  Each half runs as the
+        n-image plan over views of this slot's input, head and 'g.img' buffers (two_loss_halves): the results are
+        those of two separate n-image passes, bit for bit -- a 2n-image plan picks other tile / partition
+        parameters and rounds differently."""
+        if two_loss:
+            assert not train and not split_head and not with_targets2 and not head_bwd
+            key = "fwd.eval.%g.tl" % loss_weight
+            if key not in slot.plans:
+                halves = self.two_loss_halves(slot)
+                slot.plans[key] = PlanSeq("%s.%s" % (type(self).__name__, key),
+                                          [self.forward_plan(s, False, loss_weight) for s in halves])
+                slot.feat_hw = halves[0].feat_hw
+            return slot.plans[key]
         key = "fwd.%s.%g.%d.%d%s" % ("train" if train else "eval", loss_weight, with_targets2, split_head, ".hb" if head_bwd else "")
         if key in slot.plans:
             return slot.plans[key]
@@ -1164,10 +1197,45 @@ class PreActEngine(NetEngine):
         slot.plans[key] = P
         return P
 
-    def backward_eval_plan(self, slot: Slot, loss_weight: float, head_done: bool = False) -> Plan:
+    def two_loss_halves(self, slot: Slot):
+        """The two n-image slots of a two_loss pass over `slot` (2n images): their input, head buffers and 'g.img'
+        are views of `slot`'s; the second half's loss / counter cells are `slot`'s 'loss1' / 'correct1'."""
+        halves = getattr(slot, "two_loss_halves", None)
+        if halves is None:
+            assert slot.N % 2 == 0
+            m = slot.N // 2
+            h, x = self.head_bufs(slot), self.input(slot)
+            gimg = slot.buf("g.img", (slot.N, slot.hw, slot.hw, 8))
+            cells = ((h["loss"], h["correct"]),
+                     (slot.buf("loss1", (1,), f32, zero=True), slot.buf("correct1", (2,), torch.int32, zero=True)))
+            halves = []
+            for k in range(2):
+                s = Slot(slot.device, m, slot.hw)
+                for name in ("logits", "dlogits", "pooled", "targets", "targets2"):
+                    s.bufs[name] = h[name][k * m:(k + 1) * m]
+                s.bufs["x"], s.bufs["g.img"] = x[k * m:(k + 1) * m], gimg[k * m:(k + 1) * m]
+                s.bufs["loss"], s.bufs["correct"] = cells[k]
+                halves.append(s)
+            slot.two_loss_halves = halves
+        return halves
+
+    def _two_loss_backward(self, slot: Slot, half_weights) -> PlanSeq:
+        key = "bwd.eval.tl%g,%g" % tuple(half_weights)
+        if key not in slot.plans:
+            slot.plans[key] = PlanSeq("%s.%s" % (type(self).__name__, key),
+                                      [self.backward_eval_plan(s, float(w)) for s, w in zip(self.two_loss_halves(slot),
+                                                                                            half_weights)])
+        return slot.plans[key]
+
+    def backward_eval_plan(self, slot: Slot, loss_weight: float, head_done: bool = False, half_weights=None) -> Plan:
         """Backward of an eval-mode forward w.r.t. the input image only (Phase G: the classifier
         and clean-model weight gradients are never consumed, train_generator.py:179,254).
-        Result: slot buffer 'g.img' (bf16 NHWC c8, channels 0..2).  head_done: as backward_train_plan."""
+        Result: slot buffer 'g.img' (bf16 NHWC c8, channels 0..2).  head_done: as backward_train_plan.
+        half_weights (w0, w1): the backward of a two_loss forward -- each half's mean loss with its weight (loss_weight
+        is then unused), each half through its n-image plan."""
+        if half_weights is not None:
+            assert not head_done
+            return self._two_loss_backward(slot, half_weights)
         key = "bwd.eval.%g%s" % (loss_weight, ".hd" if head_done else "")
         if key in slot.plans:
             return slot.plans[key]
@@ -1401,9 +1469,12 @@ class ResNetEngine(PreActEngine):
         slot.plans[key] = P
         return P
 
-    def backward_eval_plan(self, slot: Slot, loss_weight: float) -> Plan:
+    def backward_eval_plan(self, slot: Slot, loss_weight: float, half_weights=None) -> Plan:
         """Input gradient of an eval-mode forward (result: 'g.img'); masks from the activated tensors, the
-        BatchNorm scales from the folded operands (bn2, shortcut) or the mask tables (bn1, stem)."""
+        BatchNorm scales from the folded operands (bn2, shortcut) or the mask tables (bn1, stem).
+        half_weights: as PreActEngine.backward_eval_plan."""
+        if half_weights is not None:
+            return self._two_loss_backward(slot, half_weights)
         key = "bwd.eval.%g" % loss_weight
         if key in slot.plans:
             return slot.plans[key]

@@ -285,6 +285,25 @@ def trigger_bwd(x, noise, p_mat, k1, noise_rate, d_out, out, l2_scale, d_noise, 
           "combat_trigger_bwd", str(tuple(x.shape)))
 
 
+def trigger_pair_fwd(x, noise, p_mat, k1, noise_rate, out_bd, out_cross, mse_partial=None) -> None:
+    """x [n] images, noise [2n] generator rows, k1 [2][3]: out_bd = T(x, noise[:n], k1[0]),
+    out_cross = T(x, noise[n:], k1[1])."""
+    n, _, hw, _ = x.shape
+    check(lib.combat_trigger_pair_fwd(x.data_ptr(), noise.data_ptr(), p_mat.data_ptr(), k1.data_ptr(), noise_rate, n, hw,
+                                      out_bd.data_ptr(), out_cross.data_ptr(), _p(mse_partial), _stream()),
+          "combat_trigger_pair_fwd", str(tuple(x.shape)))
+
+
+def trigger_pair_bwd(x, noise, p_mat, k1, noise_rate, d_bd, out_bd, l2_scale, d_cross, d_noise, pre_tanh=False,
+                     d_bd2=None) -> None:
+    """d_noise [2n]: rows [0, n) from d_bd (+ d_bd2) and the L2 term, rows [n, 2n) from d_cross."""
+    n, _, hw, _ = x.shape
+    check(lib.combat_trigger_pair_bwd(x.data_ptr(), noise.data_ptr(), p_mat.data_ptr(), k1.data_ptr(), noise_rate, n, hw,
+                                      _p(d_bd), _p(d_bd2), _p(out_bd), l2_scale, _p(d_cross), int(pre_tanh),
+                                      d_noise.data_ptr(), _stream()),
+          "combat_trigger_pair_bwd", str(tuple(x.shape)))
+
+
 def augment_fwd(x, n, hw, out_c8, params=None, index=None, out_f32=None) -> None:
     check(lib.combat_augment_fwd(x.data_ptr(), _p(index), _p(params), n, hw, out_c8.data_ptr(), _p(out_f32),
                                  _stream()), "combat_augment_fwd", "n=%d hw=%d" % (n, hw))

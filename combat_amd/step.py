@@ -16,6 +16,7 @@ kernel launches with no host synchronisation; metric counters stay on the device
 from __future__ import annotations
 
 import contextlib
+import copy
 import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
@@ -29,7 +30,7 @@ from . import ops, trigger
 from ._lib import lib
 from .augment import PostTensorTransform
 from .dist import GradReducer, bucket_ranges
-from .engine import FreqEngine, PreActEngine, UnetEngine, f32, short_workgroups
+from .engine import FreqEngine, PlanSeq, PreActEngine, UnetEngine, f32, short_workgroups
 
 BUCKETS = (8, 16, 32, 64, 128, 256, 512, 1024)
 
@@ -260,21 +261,13 @@ class AlternatedStep:
         # alone; the accuracy-only forward on the clean images goes to the second stream.
         self.sC_train = eC.slot("C.train", n, hw)
         self.merge_c = MERGE_C_EVAL and type(self) is AlternatedStep
-        if self.merge_c:
-            self.sC_eval = eC.slot("C.eval2", 2 * n, hw)   # [metric half ; loss half]
-            self.sC_met = self.sC_eval
-        else:
-            self.sC_eval = eC.slot("C.evalbd", n, hw)      # netC on the triggered images: on the critical path, so on its own
-            self.sC_met = eC.slot("C.metric", n, hw)       # netC on the clean images (accuracy only): second stream
+        self._c_eval_slots(n)
         self.sK_eval = eK.slot("K.eval2", 2 * n, hw)
         self.sG = self._gen_slot(n)
         self.sF = self.eF.slot("F", n, hw) if self.eF is not None else None
         # the heads read their labels straight out of the step table (bound before the plans marshal pointers)
         lab = self.d_targets
-        if self.merge_c:
-            self.sC_train.bufs["targets"], self.sC_eval.bufs["targets"] = lab[2], lab[0:2].view(-1)
-        else:
-            self.sC_train.bufs["targets"], self.sC_eval.bufs["targets"], self.sC_met.bufs["targets"] = lab[2], lab[1], lab[0]
+        self._c_eval_labels(lab)
         self.sK_eval.bufs["targets"], self.sK_eval.bufs["targets2"] = lab[3:5].view(-1), lab[5:7].view(-1)
         w_cm = float(self.opt.clean_model_weight)
         # one head launch per differentiated pass (forward + feature gradient: combat_head_fwd_bwd), where the engine has it
@@ -282,11 +275,10 @@ class AlternatedStep:
         self.pl = dict(
             C_train_f=eC.forward_plan(self.sC_train, True, **(dict(head_bwd=True) if hb else {})),
             C_train_b=eC.backward_train_plan(self.sC_train, **(dict(head_done=True) if hb else {})),
-            C_eval_f=eC.forward_plan(self.sC_eval, False, 1.0, False, **(dict(split_head=True) if self.merge_c else dict(head_bwd=True) if hb else {})),
+            C_eval_f=self._c_eval_fwd_plan(hb),
         )
         self.pl.update(self._gen_plans())
-        self.sC_bd = self.sC_eval.half_view(n, n, eC.FWD_SHARED) if self.merge_c else self.sC_eval
-        self.pl["C_bd_b"] = eC.backward_eval_plan(self.sC_bd, 1.0, **(dict(head_done=True) if hb and not self.merge_c else {}))
+        self.sC_bd, self.pl["C_bd_b"] = self._c_eval_bwd_plan(n, hb)
         # the second stream's passes run beside the critical queue: one tile per workgroup (engine.short_workgroups)
         with (short_workgroups() if SIDE_SHORT_WORKGROUPS else contextlib.nullcontext()):
             if not self.merge_c:
@@ -296,6 +288,48 @@ class AlternatedStep:
             self.pl["K_bd_b"] = eK.backward_eval_plan(self.sK_bd, w_cm)
             if self.sF is not None:
                 self.pl["F_f"] = self.eF.forward_plan(self.sF)
+
+    # ---- netC's eval-mode passes of Phase G (train_generator.py:227-231): slots, labels, forward, input-gradient backward
+    def _c_eval_slots(self, n) -> None:
+        eC, hw = self.eC, self.hw
+        if self.merge_c:
+            self.sC_eval = eC.slot("C.eval2", 2 * n, hw)   # [metric half ; loss half]
+            self.sC_met = self.sC_eval
+        else:
+            self.sC_eval = eC.slot("C.evalbd", n, hw)      # netC on the triggered images: on the critical path, so on its own
+            self.sC_met = eC.slot("C.metric", n, hw)       # netC on the clean images (accuracy only): second stream
+
+    def _c_eval_labels(self, lab) -> None:
+        if self.merge_c:
+            self.sC_train.bufs["targets"], self.sC_eval.bufs["targets"] = lab[2], lab[0:2].view(-1)
+        else:
+            self.sC_train.bufs["targets"], self.sC_eval.bufs["targets"], self.sC_met.bufs["targets"] = lab[2], lab[1], lab[0]
+
+    def _c_eval_fwd_plan(self, hb):
+        return self.eC.forward_plan(self.sC_eval, False, 1.0, False,
+                                    **(dict(split_head=True) if self.merge_c else dict(head_bwd=True) if hb else {}))
+
+    def _c_eval_bwd_plan(self, n, hb):
+        eC = self.eC
+        sbd = self.sC_eval.half_view(n, n, eC.FWD_SHARED) if self.merge_c else self.sC_eval
+        return sbd, eC.backward_eval_plan(sbd, 1.0, **(dict(head_done=True) if hb and not self.merge_c else {}))
+
+    def _c_eval_inputs(self, x_ptr, bd_ptr, xC, aug_ptr, n, st) -> None:
+        """The augmented images of netC's differentiated eval pass (:228; merged: + :227)."""
+        hw = self.hw
+        if self.merge_c:
+            ops.check(lib.combat_augment_fwd(x_ptr, None, aug_ptr[2], n, hw, xC.data_ptr(), None, st), "augment 2")
+            ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[3], n, hw, xC[n:].data_ptr(), None, st), "augment 3")
+        else:
+            ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[3], n, hw, xC.data_ptr(), None, st), "augment 3")
+
+    def _c_eval_grads(self, aug_ptr, n, st) -> None:
+        """Image gradient of that pass through the augmentation -> d_bd."""
+        ops.check(lib.combat_augment_bwd(self.sC_bd.bufs["g.img"].data_ptr(), 8, aug_ptr[3], n, self.hw,
+                                         self.d_bd.data_ptr(), 0, st), "augment 3 bwd")
+
+    def _fill_table_extra(self, hs, rnd, targets_cpu, bd_targets_cpu) -> None:
+        """Entries of the step table a subclass adds (staging set `hs`, before its copy)."""
 
     def _gen_slot(self, n):
         return self.eG.slot("G", n, self.hw)
@@ -377,6 +411,7 @@ class AlternatedStep:
             aug_ptr.append(self.tab_f[i].data_ptr() if a is not None else None)
         h_k1[0].copy_(torch.from_numpy(trigger.gaussian_kernel1d(rnd.sigma_c, opt.kernel_size)))
         h_k1[1].copy_(torch.from_numpy(trigger.gaussian_kernel1d(rnd.sigma_g, opt.kernel_size)))
+        self._fill_table_extra(hs, rnd, targets_cpu, bd_targets_cpu)
         # ---- the step's small copies as ONE launch (combat_copy3): table (pinned host memory, read through its device
         # mapping), batch, and the generator's re-packed output bias
         extra = self.eG.small_refresh_copy() if hasattr(self.eG, "small_refresh_copy") else None
@@ -455,11 +490,7 @@ class AlternatedStep:
 
         # ================= Phase G (train_generator.py:216-255; generator forward and clean-model chain: above) =====
         torch.cuda.current_stream().wait_event(ev_bd)
-        if self.merge_c:
-            ops.check(lib.combat_augment_fwd(x_ptr, None, aug_ptr[2], n, hw, xC.data_ptr(), None, st), "augment 2")
-            ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[3], n, hw, xC[n:].data_ptr(), None, st), "augment 3")
-        else:
-            ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[3], n, hw, xC.data_ptr(), None, st), "augment 3")
+        self._c_eval_inputs(x_ptr, bd_ptr, xC, aug_ptr, n, st)
         pl["C_eval_f"].run(prof)               # :228, :231 (merged: + :227)
         # ---- everything that is only logged (:227 accuracy of the updated netC on the clean images, :245-247
         # detector, :234-243 L2 / gradient-L2 terms) is forked to the second stream HERE: underneath the surrogate's
@@ -468,8 +499,7 @@ class AlternatedStep:
         ev_late = torch.cuda.Event()
         ev_late.record()
         pl["C_bd_b"].run(prof)
-        ops.check(lib.combat_augment_bwd(self.sC_bd.bufs["g.img"].data_ptr(), 8, aug_ptr[3], n, hw,
-                                         self.d_bd.data_ptr(), 0, st), "augment 3 bwd")
+        self._c_eval_grads(aug_ptr, n, st)
         with torch.cuda.stream(side):
             side.wait_event(ev_late)
             s2 = side.cuda_stream
@@ -645,6 +675,207 @@ class WanetStep(AlternatedStep):
             # ~640 floats travels, not the 19-MB flat buffer whose remainder is exactly zero on every rank
             lo, hi = eG.head_grad_range()
             torch.distributed.all_reduce(eG.fp.grad[lo:hi], group=self.pg)
+
+
+@dataclass
+class InputAwareRandomness(StepRandomness):
+    """The draws of one input-aware step (train_generator_inputaware.py:189-252): StepRandomness plus the blur of the
+    cross images (sigma_x) and a sixth augmentation table, aug[5] (the cross images' transform, :241)."""
+
+    sigma_x: float = 0.5
+
+
+class InputAwareStep(AlternatedStep):
+    """The alternated step of the input-aware trigger (reference train_generator_inputaware.py:170-266).  Phase C is
+    AlternatedStep's.  In Phase G the generator also runs on a second, independently shuffled batch ``inputs2``; its
+    noise is mixed onto the FIRST batch's images (``bd2``) and the surrogate is trained to keep their clean labels
+    (loss ``cross_weight * CE(netC(aug5(bd2)), targets)``, :245, :250-253).
+
+    The generator runs over [inputs ; inputs2] in one 2n slot (InstanceNorm is per sample and the UNet has no dropout,
+    so this is the reference's two calls, :231 and :236, and Phase C reads rows of the first half); its forward runs
+    the n-image plan on each half (see _gen_plans), its backward is one 2n pass.  netC's two differentiated eval
+    passes [aug3(bd) ; aug5(bd2)] share one 2n slot with two loss halves (engine two_loss / half_weights: the n-image
+    plans over its halves, so d_bd is AlternatedStep's for the same images); the paired trigger (combat_trigger_pair_fwd / _bwd) makes bd and bd2 in one launch and returns
+    the gradient of both noises in one launch.  The blur is the reference's module-level GaussianBlur (:53): kernel 3,
+    sigma in (0.1, 1), whatever --kernel_size / --sigma say (the step keeps a copy of opt with kernel_size 3 and draws
+    from SIGMA_RANGE)."""
+
+    SIGMA_RANGE = (0.1, 1.0)
+    _PER_N = AlternatedStep._PER_N + ("inputs2", "bd2", "d_cross", "_gen_bwd")
+
+    def __init__(self, netC, netG, clean_model, netF, opt, process_group=None):
+        opt = copy.copy(opt)     # the fixed blur (:53): every blur kernel of the step is built from opt.kernel_size
+        opt.kernel_size = 3
+        super().__init__(netC, netG, clean_model, netF, opt, process_group)
+        self.inputs2 = None
+        self._inputs2_src = None
+
+    def run(self, inputs: torch.Tensor, targets_cpu: torch.Tensor, inputs2: torch.Tensor,
+            rnd: Optional[InputAwareRandomness] = None, lr_c: Optional[float] = None, lr_g: Optional[float] = None,
+            prof: Optional[list] = None) -> None:
+        """inputs2: the second loader's batch (same size as inputs; device or pinned host).  lr_g defaults to the
+        reference's generator rate lr_C * 0.1 (:122)."""
+        if tuple(inputs2.shape) != tuple(inputs.shape):
+            raise ValueError("InputAwareStep: inputs2 %s must have the shape of inputs %s"
+                             % (tuple(inputs2.shape), tuple(inputs.shape)))
+        self._inputs2_src = inputs2
+        if lr_g is None:
+            lr_g = float(self.opt.lr_C) * 0.1
+        try:
+            super().run(inputs, targets_cpu, rnd, lr_c, lr_g, prof)
+        finally:
+            self._inputs2_src = None
+
+    # ---- buffers, table, plans
+    def _setup(self, n: int):
+        if n == self.N:
+            return
+        super()._setup(n)
+        if self.inputs2 is None or self.inputs2.shape[0] != n:
+            dev, hw = self.dev, self.hw
+            self.inputs2 = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)
+            self.bd2 = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)       # inputs_bd2 (:238)
+            self.d_cross = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)   # its gradient
+
+    # [6 aug tables | index_small, index_total | blur kernels of sigma_c, sigma_g, sigma_x (+ 12 bytes of padding) |
+    #  label rows]: rows 0-6 as AlternatedStep, 7 bd_targets, 8 targets (rows 7-8 = the two-half netC pass's labels)
+    @staticmethod
+    def _table_bytes(n: int) -> int:
+        return 6 * n * 16 + 2 * n * 4 + 48 + 9 * n * 8
+
+    @staticmethod
+    def _table_views(raw: torch.Tensor, n: int):
+        o1 = 6 * n * 16
+        o2 = o1 + 2 * n * 4
+        o3 = o2 + 48
+        return (raw[:o1].view(f32).view(6, n, 4), raw[o1:o2].view(torch.int32).view(2, n),
+                raw[o2:o2 + 36].view(f32).view(3, 3), raw[o3:].view(torch.int64).view(9, n))
+
+    def _fill_table_extra(self, hs, rnd, targets_cpu, bd_targets_cpu) -> None:
+        hs["k1"][2].copy_(torch.from_numpy(trigger.gaussian_kernel1d(rnd.sigma_x, self.opt.kernel_size)))
+        hs["targets"][7].copy_(bd_targets_cpu)
+        hs["targets"][8].copy_(targets_cpu)
+
+    def _gen_slot(self, n):
+        return self.eG.slot("G.pair", 2 * n, self.hw)
+
+    def _gen_plans(self) -> dict:
+        """The generator over [inputs ; inputs2] runs the n-image plans on the two halves of the 2n slot (views of its
+        buffers), forward and backward.  A 2n-image plan picks other tile and statistics partitions, and the UNet's
+        bf16 activations and 2 x 2 / 4 x 4 InstanceNorms amplify the different rounding to ~1 % of its output; with the
+        n-image plans the first half is AlternatedStep's generator pass bit for bit.  The 2n forward plan is only built
+        (it allocates the 2n buffers the halves view), never run."""
+        eG, sG = self.eG, self.sG
+        n, hw = sG.N // 2, self.hw
+        eG.forward_plan(sG)
+        sG.buf("g.z", (2 * n, hw, hw, 8))
+        share = tuple(k for k, v in sG.bufs.items() if v.dim() and v.shape[0] == sG.N)
+        halves = [sG.half_view(k * n, n, share) for k in range(2)]
+        fwd = PlanSeq("unet.fwd.halves", [eG.forward_plan(h) for h in halves])
+        self._gen_bwd = [eG.backward_plan(h) for h in halves]
+        # a half's output must land in the 2n slot ('<layer>.part': statistics partials of the half's own forward)
+        for h in halves:
+            bad = [k for k in h.bufs if k in sG.bufs and k not in share and not k.endswith(".part")]
+            assert not bad, "generator buffers not batch-major: %s" % bad
+        if getattr(self, "_g_cross", None) is None:
+            self._g_cross = torch.zeros_like(eG.fp.grad)     # the cross half's generator gradient (shared by all batch sizes)
+        return dict(G_f=fwd)
+
+    def _c_eval_slots(self, n) -> None:
+        self.sC_eval = self.eC.slot("C.cross2", 2 * n, self.hw)   # [aug3(bd) ; aug5(bd2)]: both halves differentiated
+        self.sC_met = self.eC.slot("C.metric", n, self.hw)
+
+    def _c_eval_labels(self, lab) -> None:
+        self.sC_train.bufs["targets"], self.sC_eval.bufs["targets"], self.sC_met.bufs["targets"] = \
+            lab[2], lab[7:9].view(-1), lab[0]
+
+    def _c_eval_fwd_plan(self, hb):
+        return self.eC.forward_plan(self.sC_eval, False, 1.0, False, two_loss=True)
+
+    def _c_eval_bwd_plan(self, n, hb):
+        return self.sC_eval, self.eC.backward_eval_plan(self.sC_eval, 1.0, half_weights=(1.0, float(self.opt.cross_weight)))
+
+    # ---- the step's pieces
+    def _draw(self, targets_cpu, bd_targets_cpu) -> InputAwareRandomness:
+        """Reference order (:189-252): num_bd, sigma_c (only if num_bd > 0), aug0, aug1, sigma_g, sigma_x, aug2, aug5
+        (cross images, :241), aug3, aug4."""
+        n = targets_cpu.shape[0]
+        n_trg = int((targets_cpu == bd_targets_cpu).sum())
+        num_bd = int(np.sum(np.random.rand(n_trg) < self.opt.pc))
+        sigma_c = trigger.sample_sigma(self.SIGMA_RANGE) if num_bd else 0.5
+        aug0, aug1 = self.transforms.sample(n), self.transforms.sample(n)
+        sigma_g = trigger.sample_sigma(self.SIGMA_RANGE)
+        sigma_x = trigger.sample_sigma(self.SIGMA_RANGE)
+        aug2, aug5, aug3, aug4 = (self.transforms.sample(n) for _ in range(4))
+        return InputAwareRandomness(num_bd, sigma_c, sigma_g, [aug0, aug1, aug2, aug3, aug4, aug5], sigma_x=sigma_x)
+
+    def _gen_forward(self, x_ptr, n, st, prof) -> None:
+        """netG over [inputs ; inputs2].  The second batch's copy sits next to the step's combat_copy3 (it comes from
+        its own loader's pinned ring)."""
+        self.inputs2.copy_(self._inputs2_src, non_blocking=True)
+        gin = self.eG.input(self.sG)
+        ops.check(lib.combat_image_to_c8(x_ptr, n, self.hw, gin.data_ptr(), st), "c8 G")
+        ops.check(lib.combat_image_to_c8(self.inputs2.data_ptr(), n, self.hw, gin[n:].data_ptr(), st), "c8 G2")
+        self.pl["G_f"].run(prof)
+
+    def _trigger_g(self, x_ptr, n, k1g, s2) -> None:
+        """inputs_bd (blur sigma_g, + squared-error partials) and inputs_bd2 (sigma_x), both on the first batch's
+        images (:231-238): one launch."""
+        ops.check(lib.combat_trigger_pair_fwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1g,
+                                              float(self.opt.noise_rate), n, self.hw, self.bd.data_ptr(),
+                                              self.bd2.data_ptr(), self.mse.data_ptr(), s2), "trigger pair")
+
+    def _c_eval_inputs(self, x_ptr, bd_ptr, xC, aug_ptr, n, st) -> None:
+        hw = self.hw
+        ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[3], n, hw, xC.data_ptr(), None, st), "augment 3")
+        ops.check(lib.combat_augment_fwd(self.bd2.data_ptr(), None, aug_ptr[5], n, hw, xC[n:].data_ptr(), None, st),
+                  "augment 5")
+
+    def _c_eval_grads(self, aug_ptr, n, st) -> None:
+        g = self.sC_eval.bufs["g.img"]
+        ops.check(lib.combat_augment_bwd(g.data_ptr(), 8, aug_ptr[3], n, self.hw, self.d_bd.data_ptr(), 0, st),
+                  "augment 3 bwd")
+        ops.check(lib.combat_augment_bwd(g[n:].data_ptr(), 8, aug_ptr[5], n, self.hw, self.d_cross.data_ptr(), 0, st),
+                  "augment 5 bwd")
+
+    def _gen_backward(self, x_ptr, n, k1g, st, prof) -> None:
+        """Both noises' gradients in one launch (rows [0, n): d_bd + d_bd2 + the L2 term; rows [n, 2n): d_cross), then
+        the generator backward of each half (:253-254).  A backward plan starts by zeroing the gradient buffer, so the
+        cross half runs first and its gradient is set aside; the first half's backward is then AlternatedStep's, and
+        the cross gradient is added to it (exactly nothing at cross_weight 0)."""
+        hw = self.hw
+        l2_scale = float(self.opt.L2_weight) / float(n * 3 * hw * hw)
+        ops.check(lib.combat_trigger_pair_bwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1g,
+                                              float(self.opt.noise_rate), n, hw, self.d_bd.data_ptr(),
+                                              self.d_bd2.data_ptr(), self.bd.data_ptr(), l2_scale, self.d_cross.data_ptr(),
+                                              1, self.sG.buf("g.z", (2 * n, hw, hw, 8)).data_ptr(), st), "trigger pair bwd")
+        grad = self.eG.fp.grad
+        self._gen_bwd[1].run(prof)
+        self._g_cross.copy_(grad)
+        self._gen_bwd[0].run(prof)
+        grad.add_(self._g_cross)
+        if self.world > 1 or (FORCE_ALLREDUCE and self.pg is not None):
+            torch.distributed.all_reduce(grad, group=self.pg)   # one flat all-reduce (the multi-rank path is untested)
+
+    # ---- metrics
+    def read_metrics(self, reset: bool = False) -> Dict[str, float]:
+        """AlternatedStep's keys plus loss_cross_sum (sum of the per-step CE(pred_cross, targets)) and cross_correct
+        (#argmax(pred_cross) == targets, :275)."""
+        out = super().read_metrics(reset=False)
+        out["loss_cross_sum"], out["cross_correct"] = 0.0, 0
+        for _, sCe, _, _ in self._slot_sets():
+            out["loss_cross_sum"] += float(sCe.bufs["loss1"])
+            out["cross_correct"] += int(sCe.bufs["correct1"][0])
+        if reset:
+            self.reset_metrics()
+        return out
+
+    def reset_metrics(self) -> None:
+        super().reset_metrics()
+        for _, sCe, _, _ in self._slot_sets():
+            for k in ("loss1", "correct1"):
+                if k in sCe.bufs:
+                    sCe.bufs[k].zero_()
 
 
 def _zero_grad(fp, st):

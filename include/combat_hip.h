@@ -398,6 +398,21 @@ int combat_trigger_fwd(const float *x, const void *noise, const float *P, const 
 int combat_trigger_bwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
                        int32_t n, int32_t hw, const float *d_out, const float *d_out2 /* NULL, or added to d_out */,
                        const float *out, float l2_scale, int32_t pre_tanh, void *d_noise, void *stream);
+/* Paired trigger of the input-aware step (train_generator_inputaware.py:231-238, 263-266): the generator ran on
+ * [inputs ; inputs2] (noise: 2n c8 rows) and BOTH noises are mixed onto the first batch's images x [n].
+ * k1: fp32 [2][3], the blur of out_bd, then the blur of out_cross (two draws of the module-level GaussianBlur, :53).
+ *   out_bd[i]    = T(x[i], noise[i],     k1[0])   + mse_partial [3n] as combat_trigger_fwd
+ *   out_cross[i] = T(x[i], noise[n + i], k1[1])
+ * Backward, one launch over the 2n rows of d_noise: rows [0, n) get what combat_trigger_bwd(d_bd, d_bd2, out_bd,
+ * l2_scale) writes, rows [n, 2n) what combat_trigger_bwd(d_cross) writes (no L2 term: the reference's MSELoss reads
+ * inputs_bd only, :250).  Per image the arithmetic of the single-noise entry points, in the same order: the results
+ * are bit-identical to two calls of them. */
+int combat_trigger_pair_fwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
+                            int32_t n, int32_t hw, float *out_bd, float *out_cross, float *mse_partial, void *stream);
+int combat_trigger_pair_bwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
+                            int32_t n, int32_t hw, const float *d_bd, const float *d_bd2 /* NULL, or added to d_bd */,
+                            const float *out_bd, float l2_scale, const float *d_cross /* NULL: zero */, int32_t pre_tanh,
+                            void *d_noise, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * PostTensorTransform (utils/dataloader.py:45-60): per-sample crop(pad, integer offset) ->

@@ -1,0 +1,292 @@
+"""Alternated training with the input-aware (cross-trigger) objective on MI355X.
+
+Drop-in for the reference script of the same name (reference train_generator_inputaware.py:81-138 get_model,
+:141-336 train, :339-508 eval, :511-686 main): the networks, trigger, augmentation and detector are
+train_generator.py's.  What differs, and is added here:
+  * a second, independently shuffled train loader and a second (shuffled) test loader (:535-538); the generator
+    also runs on their batches and that noise is mixed onto the FIRST batch's images ("cross" images, which the
+    surrogate must keep on their clean label: loss weight --cross_weight);
+  * optimizerG is SGD at lr_C * 0.1 and schedulerG steps on the C milestones (:120-127);
+  * the blur is the module-level T.GaussianBlur(kernel_size=3, sigma=(0.1, 1)) (:53): --kernel_size / --sigma are
+    ignored, as they are there;
+  * "Cross Acc" in the progress line, tensorboard ("Cross") and eval (counted on the non-target-class rows,
+    divided by the number of those rows, :405-414);
+  * the checkpoint adds best_cross_acc and the (unused) mask / pattern tensors (:480-498), restored on
+    --continue_training (:597-618).
+The per-batch body (:170-290) runs as ``combat_amd.step.InputAwareStep`` on the HIP kernels.
+
+Data parallel: ``python -m torch.distributed.run --nproc-per-node N ...`` shards BOTH train loaders like the first
+(combat_amd.dist).  That path has not been run on more than one GPU.
+"""
+import os
+import random
+import time
+
+import numpy as np
+import torch
+
+import config
+import train_generator as base
+from combat_amd import api, dist as cdist
+from combat_amd.data import get_dataloader
+from combat_amd.log import SummaryWriter, image_grid, progress_bar
+from combat_amd.nets import configure_dataset
+from combat_amd.step import InputAwareStep, create_targets_bd  # noqa: F401  (re-exported like the reference)
+
+create_dir = base.create_dir
+SECOND_LOADER_SEED = 104729    # offset of the second train loader's permutation seed when --seed is given
+
+
+def fix_blur(opt):
+    """gauss_smooth = T.GaussianBlur(kernel_size=3, sigma=(0.1, 1)) (:53), whatever the flags say."""
+    opt.kernel_size = 3
+    opt.sigma = (0.1, 1.0)
+
+
+def get_model(opt):
+    netC, optimizerC, schedulerC, netG, _, _, netF, clean_model = base.get_model(opt)
+    optimizerG = torch.optim.SGD(netG.parameters(), opt.lr_C * 0.1, momentum=0.9, weight_decay=5e-4, nesterov=True)
+    schedulerG = torch.optim.lr_scheduler.MultiStepLR(optimizerG, opt.schedulerC_milestones, opt.schedulerC_lambda)
+    return netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model
+
+
+def _step_of(netC, netG, clean_model, netF, opt) -> InputAwareStep:
+    st = netC.__dict__.get("_ia_step")
+    if st is None:
+        pg = torch.distributed.group.WORLD if torch.distributed.is_initialized() else None
+        st = InputAwareStep(netC, netG, clean_model, netF, opt, process_group=pg)
+        netC.__dict__["_ia_step"] = st
+    return st
+
+
+def _rows_like(x2, n):
+    """The second loader's batch cut (or wrapped) to n rows: under data parallel a shuffled loader pads its shard
+    while the evaluation loader keeps exact shards, so the last batches may differ in size."""
+    if x2.shape[0] == n:
+        return x2
+    reps = (n + x2.shape[0] - 1) // x2.shape[0]
+    return torch.cat([x2] * reps)[:n]
+
+
+def train(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, train_dl, train_dl2, mask,
+          pattern, tf_writer, epoch, opt):
+    print(" Train:")
+    netC.train()
+    netG.train()
+    clean_model.eval()
+    st = _step_of(netC, netG, clean_model, netF, opt)
+    st.reset_metrics()
+    n_batches = len(train_dl)
+    every = max(1, int(getattr(opt, "log_interval", 20)))
+    m = None
+    for batch_idx, (inputs, targets), (inputs2, _) in zip(range(n_batches), train_dl, train_dl2):
+        inputs2 = _rows_like(inputs2, inputs.shape[0])
+        st.run(inputs.to(opt.device, non_blocking=True), targets, inputs2.to(opt.device, non_blocking=True),
+               lr_c=optimizerC.param_groups[0]["lr"], lr_g=optimizerG.param_groups[0]["lr"])
+        last = batch_idx == n_batches - 1 or (opt.max_steps and batch_idx + 1 >= opt.max_steps)
+        if batch_idx % every == 0 or last:
+            m = st.read_metrics()
+            ts = m["samples"]
+            progress_bar(
+                batch_idx, n_batches,
+                "Clean Acc: {:.4f} | Bd Acc: {:.4f} | F Acc: {:.4f} | Cross Acc: {:.4f} | Clean Model Acc: {:.4f} | "
+                "Clean Model Bd BA: {:.4f} | Clean Model Bd ASR: {:.4f}".format(
+                    m["clean_correct"] * 100.0 / ts, m["bd_correct"] * 100.0 / ts, m["f_correct"] * 100.0 / ts,
+                    m["cross_correct"] * 100.0 / ts, m["clean_model_correct"] * 100.0 / ts,
+                    m["clean_model_bd_ba"] * 100.0 / ts, m["clean_model_bd_asr"] * 100.0 / ts))
+        if last:
+            break
+    ts = m["samples"]
+    if not epoch % 1:
+        tf_writer.add_scalars("Clean Accuracy", {
+            "Clean": m["clean_correct"] * 100.0 / ts, "Bd": m["bd_correct"] * 100.0 / ts,
+            "Cross": m["cross_correct"] * 100.0 / ts, "F": m["f_correct"] * 100.0 / ts,
+            "CleanModel Acc": m["clean_model_correct"] * 100.0 / ts,
+            "CleanModel Bd BA": m["clean_model_bd_ba"] * 100.0 / ts,
+            "CleanModel Bd ASR": m["clean_model_bd_asr"] * 100.0 / ts,
+            "L2 Loss": m["loss_l2_sum"] / ts, "CleanModel Loss": m["clean_model_loss_sum"] / ts}, epoch)
+        if not isinstance(tf_writer, cdist.NullWriter):     # :310-331: the last batch and its backdoored copy
+            tf_writer.add_image("Images", image_grid(st.inputs, st.bd, opt), global_step=epoch)
+    schedulerC.step()
+    schedulerG.step()
+
+
+def eval(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, test_dl, test_dl2, mask, pattern,
+         best_clean_acc, best_bd_acc, best_cross_acc, best_F_acc, best_clean_model_acc, best_clean_model_bd_ba,
+         best_clean_model_bd_asr, tf_writer, epoch, opt):
+    print(" Eval:")
+    netC.eval()
+    cdist.average_bn_buffers(netC)
+    netG.eval()
+    clean_model.eval()
+    c = dict(clean_n=0, bd_n=0, clean=0, bd=0, cross=0, F=0, cm=0, cm_ba=0, cm_asr=0)
+    n_batches = len(test_dl)
+    for batch_idx, (inputs, targets), (inputs2, _) in zip(range(n_batches), test_dl, test_dl2):
+        with torch.no_grad():
+            inputs, targets = inputs.to(opt.device), targets.to(opt.device)
+            inputs2 = _rows_like(inputs2, inputs.shape[0]).to(opt.device)
+            preds_clean = netC(inputs)
+            c["clean_n"] += len(inputs)
+            ntrg = (targets != opt.target_label).nonzero()[:, 0]
+            inputs_toChange, targets_toChange = inputs[ntrg], targets[ntrg]
+            inputs_bd = api.create_backdoor(netG, inputs_toChange, opt)                 # :395-397
+            targets_bd = create_targets_bd(targets_toChange, opt).to(opt.device)
+            c["bd_n"] += len(ntrg)
+            inputs_cross = api.create_backdoor(netG, inputs, opt, noise_from=inputs2)    # :405-407: the WHOLE batch
+            cnt = [(preds_clean.argmax(1) == targets).sum(), (clean_model(inputs).argmax(1) == targets).sum()]
+            if len(ntrg):
+                preds_bd = netC(inputs_bd)
+                cm_bd = clean_model(inputs_bd).argmax(1)
+                preds_cross = netC(inputs_cross)
+                cnt += [(preds_bd.argmax(1) == targets_bd).sum(),
+                        (api.frequency_logits(netF, inputs_bd, opt).argmax(1) == 1).sum(),
+                        (cm_bd == targets_toChange).sum(), (cm_bd == targets_bd).sum(),
+                        (preds_cross[ntrg].argmax(1) == targets[ntrg]).sum()]         # :410-414: non-target rows only
+            cnt = torch.stack(cnt).cpu().tolist()
+            c["clean"] += int(cnt[0])
+            c["cm"] += int(cnt[1])
+            if len(ntrg):
+                c["bd"] += int(cnt[2])
+                c["F"] += int(cnt[3])
+                c["cm_ba"] += int(cnt[4])
+                c["cm_asr"] += int(cnt[5])
+                c["cross"] += int(cnt[6])
+        acc = _accuracies(c)
+        progress_bar(batch_idx, n_batches,
+                     "Clean Acc: {:.4f} - Best: {:.4f} | Bd Acc: {:.4f} - Best: {:.4f} | Cross Acc: {:.4f} - Best: {:.4f} | "
+                     "F Acc: {:.4f} - Best: {:.4f} | Clean Model BA: {:.4f} - Best: {:.4f} | Clean Model Bd BA: {:.4f} - "
+                     "Best: {:.4f} | Clean Model Bd ASR: {:.4f} - Best: {:.4f}".format(
+                         acc["clean"], best_clean_acc, acc["bd"], best_bd_acc, acc["cross"], best_cross_acc, acc["F"],
+                         best_F_acc, acc["cm"], best_clean_model_acc, acc["cm_ba"], best_clean_model_bd_ba,
+                         acc["cm_asr"], best_clean_model_bd_asr))
+    if torch.distributed.is_initialized():
+        vals = cdist.all_reduce_counters([c[k] for k in sorted(c)], device=opt.device)
+        c = dict(zip(sorted(c), vals))
+        acc = _accuracies(c)
+    if not epoch % 1:
+        tf_writer.add_scalars("Test Accuracy", {
+            "Clean": acc["clean"], "Bd": acc["bd"], "Cross": acc["cross"], "F": acc["F"], "Clean Model Acc": acc["cm"],
+            "Clean Model Bd BA": acc["cm_ba"], "Clean Model Bd ASR": acc["cm_asr"]}, epoch)
+    if acc["clean"] > best_clean_acc:     # :471 (no tie-break, unlike train_generator.py)
+        print(" Saving...")
+        best_clean_acc, best_bd_acc, best_cross_acc, best_F_acc = acc["clean"], acc["bd"], acc["cross"], acc["F"]
+        best_clean_model_acc, best_clean_model_bd_ba, best_clean_model_bd_asr = acc["cm"], acc["cm_ba"], acc["cm_asr"]
+        if int(os.environ.get("RANK", 0)) == 0:
+            api.sync_momentum_to_optimizer(optimizerC, netC)
+            api.sync_momentum_to_optimizer(optimizerG, netG)
+            torch.save({
+                "netC": netC.state_dict(), "schedulerC": schedulerC.state_dict(), "optimizerC": optimizerC.state_dict(),
+                "netG": netG.state_dict(), "schedulerG": schedulerG.state_dict(), "optimizerG": optimizerG.state_dict(),
+                "clean_model": clean_model.state_dict(), "best_clean_acc": best_clean_acc, "best_bd_acc": best_bd_acc,
+                "best_cross_acc": best_cross_acc, "best_F_acc": best_F_acc, "best_clean_model_acc": best_clean_model_acc,
+                "best_clean_model_bd_ba": best_clean_model_bd_ba, "best_clean_model_bd_asr": best_clean_model_bd_asr,
+                "epoch_current": epoch, "mask": mask, "pattern": pattern}, opt.ckpt_path)
+    return (best_clean_acc, best_bd_acc, best_cross_acc, best_F_acc, best_clean_model_acc, best_clean_model_bd_ba,
+            best_clean_model_bd_asr)
+
+
+def _accuracies(c):
+    bd_n = max(c["bd_n"], 1)
+    return dict(clean=c["clean"] * 100.0 / c["clean_n"], bd=c["bd"] * 100.0 / bd_n, cross=c["cross"] * 100.0 / bd_n,
+                F=c["F"] * 100.0 / bd_n, cm=c["cm"] * 100.0 / c["clean_n"], cm_ba=c["cm_ba"] * 100.0 / bd_n,
+                cm_asr=c["cm_asr"] * 100.0 / bd_n)
+
+
+BEST_KEYS = ("best_clean_acc", "best_bd_acc", "best_cross_acc", "best_F_acc", "best_clean_model_acc",
+             "best_clean_model_bd_ba", "best_clean_model_bd_asr")
+
+
+def main():
+    opt = config.get_arguments().parse_args()
+    configure_dataset(opt)
+    fix_blur(opt)
+    rank, local_rank, world = cdist.init()
+    if opt.device == "cuda":
+        opt.device = "cuda:%d" % local_rank
+    if opt.seed is not None:
+        torch.manual_seed(opt.seed)
+        np.random.seed(opt.seed + rank)
+        random.seed(opt.seed + rank)
+
+    train_dl = get_dataloader(opt, True, rank=rank, world=world)
+    test_dl = get_dataloader(opt, False, shuffle=False, rank=rank, world=world)
+    train_dl2 = get_dataloader(opt, True, rank=rank, world=world)
+    test_dl2 = get_dataloader(opt, False, rank=rank, world=world)      # shuffled, as the reference's (:538)
+    if opt.seed is not None:     # a seeded loader derives its permutations from --seed: keep the two train orders apart
+        train_dl2.base_seed += SECOND_LOADER_SEED
+        test_dl2.base_seed += SECOND_LOADER_SEED
+    netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model = get_model(opt)
+
+    mode = opt.saving_prefix
+    opt.ckpt_folder = os.path.join(opt.checkpoints, "{}_clean".format(mode), opt.dataset)
+    opt.ckpt_path = os.path.join(opt.ckpt_folder, "{}_{}_clean.pth.tar".format(opt.dataset, mode))
+    opt.log_dir = os.path.join(opt.ckpt_folder, "log_dir")
+
+    opt.F_ckpt_path = base.detector_checkpoint_path(opt)
+    print(f"Loading {opt.F_model} at {opt.F_ckpt_path}")
+    if os.path.exists(opt.F_ckpt_path):
+        netF.load_state_dict(torch.load(opt.F_ckpt_path, map_location=opt.device, weights_only=True)["netC"])
+    elif not opt.allow_missing_F:
+        print("Error: {} not found (pass --allow_missing_F to run with an untrained detector)".format(opt.F_ckpt_path))
+        exit()
+    netF.eval()
+    print("Done")
+
+    load_path = os.path.join(opt.checkpoints, opt.load_checkpoint_clean or "", opt.dataset,
+                             "{}_{}.pth.tar".format(opt.dataset, opt.load_checkpoint_clean))
+    if not os.path.exists(load_path):
+        print("Error: {} not found".format(load_path))
+        exit()
+    clean_model.load_state_dict(torch.load(load_path, map_location=opt.device, weights_only=True)["netC"])
+    clean_model.eval()
+
+    if opt.continue_training:
+        if not os.path.exists(opt.ckpt_path):
+            print("Pretrained model doesnt exist")
+            exit()
+        print("Continue training!!")
+        sd = torch.load(opt.ckpt_path, map_location=opt.device, weights_only=True)
+        netC.load_state_dict(sd["netC"])
+        optimizerC.load_state_dict(sd["optimizerC"])
+        schedulerC.load_state_dict(sd["schedulerC"])
+        netG.load_state_dict(sd["netG"])
+        optimizerG.load_state_dict(sd["optimizerG"])
+        schedulerG.load_state_dict(sd["schedulerG"])
+        clean_model.load_state_dict(sd["clean_model"])
+        api.load_momentum_from_optimizer(optimizerC, netC)
+        api.load_momentum_from_optimizer(optimizerG, netG)
+        best = [sd[k] for k in BEST_KEYS]
+        epoch_current = sd["epoch_current"]
+        mask, pattern = sd["mask"].to(opt.device), sd["pattern"].to(opt.device)
+    else:
+        print("Train from scratch!!!")
+        best = [0.0] * len(BEST_KEYS)
+        epoch_current = 0
+        mask = torch.zeros(opt.input_height, opt.input_width, device=opt.device)     # :621-623 (saved, never used)
+        mask[2:6, 2:6] = 0.1
+        pattern = torch.rand(opt.input_channel, opt.input_height, opt.input_width).to(opt.device)
+        cdist.fresh_start(opt.ckpt_folder, rank)
+    if world > 1:
+        for m in (netC, netG, clean_model, netF):
+            cdist.broadcast_module(m)
+    if rank == 0:
+        create_dir(opt.log_dir)
+        tf_writer = SummaryWriter(log_dir=opt.log_dir)
+    else:
+        tf_writer = cdist.NullWriter()
+
+    train_dl.epoch = train_dl2.epoch = epoch_current
+    for epoch in range(epoch_current, opt.n_iters):
+        print("Epoch {}:".format(epoch + 1))
+        t0 = time.perf_counter()
+        train(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, train_dl, train_dl2, mask,
+              pattern, tf_writer, epoch, opt)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        best = list(eval(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, test_dl, test_dl2,
+                         mask, pattern, *best, tf_writer, epoch, opt))
+        print(" train {:.2f} s, eval + checkpoint {:.2f} s".format(t1 - t0, time.perf_counter() - t1))
+
+
+if __name__ == "__main__":
+    main()

@@ -101,8 +101,13 @@ def load_generator(netG, load_path, opt):
     netG.requires_grad_(False)      # :279-280
 
 
-def main(get_model=None, wanet=False):
+def main(get_model=None, wanet=False, eval=None, clean_folder=None):
+    """``get_model`` / ``eval`` default to this module's: train_victim_wanet.py passes its own get_model,
+    train_victim_inputaware.py its own get_model and eval.  clean_folder (default: wanet): the checkpoint lives under
+    <saving_prefix>_clean/."""
     get_model = get_model or globals()["get_model"]
+    eval = eval or globals()["eval"]
+    clean_folder = wanet if clean_folder is None else clean_folder
     opt = config.get_arguments().parse_args()
     configure_dataset(opt)
     rank, local_rank, world = cdist.init()
@@ -118,7 +123,7 @@ def main(get_model=None, wanet=False):
     test_dl = get_dataloader(opt, False, shuffle=False, poisoned=True, rank=rank, world=world)
     netC, optimizerC, schedulerC, netG = get_model(opt)
     # train_victim.py:255-257 saves under <prefix>/, train_victim_wanet.py:241-243 under <prefix>_clean/
-    mode = "{}_clean".format(opt.saving_prefix) if wanet else opt.saving_prefix
+    mode = "{}_clean".format(opt.saving_prefix) if clean_folder else opt.saving_prefix
     opt.ckpt_folder = os.path.join(opt.checkpoints, mode, opt.dataset)
     opt.ckpt_path = os.path.join(opt.ckpt_folder, "{}_{}.pth.tar".format(opt.dataset, mode))
     opt.log_dir = os.path.join(opt.ckpt_folder, "log_dir")
