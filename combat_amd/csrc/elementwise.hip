@@ -440,10 +440,14 @@ inline unsigned grid_for(long total, int cap = 4096) {
 //             taken of delta = x - xb
 //   hits   += #{images : logits[i][1] > logits[i][0]}                           detector says "backdoor" (argmax == 1)
 // Workgroup = one (image, channel) plane; fp64 accumulators, one atomic per workgroup and term.
-__global__ __launch_bounds__(256) void log_terms_kernel(const float *__restrict__ x, const float *__restrict__ xb,
-                                                        const float *__restrict__ mse_partial, int n_partial, int n, int hw,
-                                                        const float *__restrict__ logits, int n_logits,
-                                                        double *__restrict__ acc, double *__restrict__ hits, double *__restrict__ part) {
+// TV (the imperceptible step, train_generator_imperceptible.py:228, :245): acc[2] += sum(tv_partial) / n, the batch mean
+// of the per-image total variation, from the trigger kernel's per-plane sums (tv_partial [3n]).  The planes are added
+// in index order by one thread, in every mode.
+template <bool TV>
+__device__ __forceinline__ void log_terms_body(const float *__restrict__ x, const float *__restrict__ xb,
+                                               const float *__restrict__ mse_partial, const float *__restrict__ tv_partial,
+                                               int n_partial, int n, int hw, const float *__restrict__ logits, int n_logits,
+                                               double *__restrict__ acc, double *__restrict__ hits, double *__restrict__ part) {
     __shared__ float red[2][256];
     const int tid = threadIdx.x, plane = blockIdx.x;
     const float *px = x + (long)plane * hw * hw, *pb = xb + (long)plane * hw * hw;
@@ -504,7 +508,37 @@ __global__ __launch_bounds__(256) void log_terms_kernel(const float *__restrict_
             }
             if (tid == 0) atomicAdd(hits, (double)rh[0]);
         }
+        if (TV) {
+            __shared__ float tvp[256];
+            double s = 0.0;
+            for (int base = 0; base < n_partial; base += 256) {      // staged 256 planes at a time, added by thread 0
+                tvp[tid] = base + tid < n_partial ? tv_partial[base + tid] : 0.f;
+                __syncthreads();
+                if (tid == 0) {
+                    const int m = n_partial - base < 256 ? n_partial - base : 256;
+#pragma unroll 16
+                    for (int i = 0; i < m; ++i) s += (double)tvp[i];
+                }
+                __syncthreads();
+            }
+            if (tid == 0) acc[2] += s / (double)n;       // this thread is the cell's only writer
+        }
     }
+}
+
+__global__ __launch_bounds__(256) void log_terms_kernel(const float *__restrict__ x, const float *__restrict__ xb,
+                                                        const float *__restrict__ mse_partial, int n_partial, int n, int hw,
+                                                        const float *__restrict__ logits, int n_logits,
+                                                        double *__restrict__ acc, double *__restrict__ hits, double *__restrict__ part) {
+    log_terms_body<false>(x, xb, mse_partial, nullptr, n_partial, n, hw, logits, n_logits, acc, hits, part);
+}
+
+__global__ __launch_bounds__(256) void log_terms_tv_kernel(const float *__restrict__ x, const float *__restrict__ xb,
+                                                           const float *__restrict__ mse_partial,
+                                                           const float *__restrict__ tv_partial, int n_partial, int n, int hw,
+                                                           const float *__restrict__ logits, int n_logits,
+                                                           double *__restrict__ acc, double *__restrict__ hits, double *__restrict__ part) {
+    log_terms_body<true>(x, xb, mse_partial, tv_partial, n_partial, n, hw, logits, n_logits, acc, hits, part);
 }
 
 __global__ void log_terms_finish_kernel(const double *__restrict__ part, int planes, double *__restrict__ acc) {
@@ -657,6 +691,22 @@ extern "C" int combat_log_terms(const float *x, const float *xb, const float *ms
     CB_LAUNCH_CHECK();
     if (part) {
         COMBAT_LAUNCH(log_terms_finish_kernel, dim3(1), dim3(1), 0, as_stream(stream), (const double *)part, 3 * n, acc2);
+        CB_LAUNCH_CHECK();
+    }
+    return COMBAT_OK;
+}
+
+extern "C" int combat_log_terms_tv(const float *x, const float *xb, const float *mse_partial, const float *tv_partial,
+                                   int32_t n, int32_t hw, const float *detector_logits, double *acc3, double *hits,
+                                   void *stream) {
+    COMBAT_PLAN_HOOK(combat_log_terms_tv, x, xb, mse_partial, tv_partial, n, hw, detector_logits, acc3, hits);
+    if (!x || !xb || !tv_partial || !acc3 || n <= 0 || hw < 2) return COMBAT_EINVAL;
+    double *part = combat_deterministic() ? reinterpret_cast<double *>(combat_stream_scratch(stream, (size_t)3 * n * sizeof(double))) : nullptr;
+    COMBAT_LAUNCH(log_terms_tv_kernel, dim3(3 * n), dim3(256), 0, as_stream(stream), x, xb, mse_partial, tv_partial, 3 * n,
+                       n, hw, detector_logits, n, acc3, hits, part);
+    CB_LAUNCH_CHECK();
+    if (part) {
+        COMBAT_LAUNCH(log_terms_finish_kernel, dim3(1), dim3(1), 0, as_stream(stream), (const double *)part, 3 * n, acc3);
         CB_LAUNCH_CHECK();
     }
     return COMBAT_OK;

@@ -86,10 +86,17 @@ __device__ __forceinline__ void store_hilo(__bf16 *px8, int c, float v) {   // h
 // B [hw][hw+1].  P is symmetric (D^T diag(mask) D), so P N P^T = (P N) P needs no transposed operand.
 // The per-(channel, image) body, shared by trigger_fwd_kernel and trigger_pair_fwd_kernel: xi is the image's plane
 // of channel c, nz its noise pixels (c8), outp its output plane (the image's row `img` of out_c8 / mse).
+// TV (the imperceptible step, train_generator_imperceptible.py:228): the plane's total variation
+// sum |out[y+1][x] - out[y][x]| + sum |out[y][x+1] - out[y][x]| -> tv[3 img + c], taken from the blurred plane while it
+// is still in LDS (unit-stride reads of the pitch-hw plane A: no bank conflict).  Each thread adds its pixels in index
+// order, the 64 lanes of a wave are folded by shuffles and the four wave sums added in wave order: the same bits every
+// run.  out and mse are computed by the same instructions with and without TV.
+template <bool TV>
 __device__ __forceinline__ void trigger_fwd_plane(float *sm, const float *__restrict__ xi, const __bf16 *__restrict__ nz,
                                                   const float *__restrict__ P, const float *__restrict__ k1, float rate,
                                                   int hw, int c, long img, float *__restrict__ outp,
-                                                  __bf16 *__restrict__ out_c8, float *__restrict__ mse) {
+                                                  __bf16 *__restrict__ out_c8, float *__restrict__ mse,
+                                                  float *__restrict__ tv) {
     const int hw2 = hw * hw, lp = hw + 1, tid = threadIdx.x;
     float *Pl = sm, *Pr = Pl + hw * lp, *A = Pr + hw2, *B = A + hw2;
     const float kk[3] = {k1[0], k1[1], k1[2]};
@@ -110,13 +117,18 @@ __device__ __forceinline__ void trigger_fwd_plane(float *sm, const float *__rest
     __syncthreads();
     blur_pass<false, false>(B, A, kk, hw, tid);  // ... * Kb^T
     __syncthreads();
-    float se = 0.f;
+    float se = 0.f, tvs = 0.f;
     for (int o = tid; o < hw2; o += 256) {
         const float v = A[o];
         outp[o] = v;
         const float d = v - xi[o];
         se = fmaf(d, d, se);
         if (out_c8) store_hilo(out_c8 + (img * hw2 + o) * 8, c, v);
+        if (TV) {
+            const int y = o / hw, xx = o - y * hw;
+            if (y + 1 < hw) tvs += fabsf(A[o + hw] - v);
+            if (xx + 1 < hw) tvs += fabsf(A[o + 1] - v);
+        }
     }
     if (mse) {
         __syncthreads();
@@ -128,6 +140,12 @@ __device__ __forceinline__ void trigger_fwd_plane(float *sm, const float *__rest
         }
         if (tid == 0) mse[img * 3 + c] = B[0];
     }
+    if (TV) {
+        for (int d = 32; d > 0; d >>= 1) tvs += __shfl_down(tvs, d, 64);
+        if ((tid & 63) == 0) Pl[tid >> 6] = tvs;      // Pl: last read by the first product
+        __syncthreads();
+        if (tid == 0) tv[img * 3 + c] = ((Pl[0] + Pl[1]) + Pl[2]) + Pl[3];
+    }
 }
 
 __global__ __launch_bounds__(256) void trigger_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
@@ -138,8 +156,19 @@ __global__ __launch_bounds__(256) void trigger_fwd_kernel(const float *__restric
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int hw2 = hw * hw, c = blockIdx.x, img = blockIdx.y;
     const long src = src_index ? src_index[img] : img;   // row of x / noise this output image is made from
-    trigger_fwd_plane(sm, x + (src * 3 + c) * hw2, noise + src * hw2 * 8, P, k1, rate, hw, c, img,
-                      out + ((long)img * 3 + c) * hw2, out_c8, mse);
+    trigger_fwd_plane<false>(sm, x + (src * 3 + c) * hw2, noise + src * hw2 * 8, P, k1, rate, hw, c, img,
+                             out + ((long)img * 3 + c) * hw2, out_c8, mse, nullptr);
+}
+
+// trigger_fwd_kernel + the per-plane total variation of `out` (no src_index / out_c8: Phase G mixes the whole batch).
+__global__ __launch_bounds__(256) void trigger_tv_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                             const float *__restrict__ P, const float *__restrict__ k1,
+                                                             float rate, int hw, float *__restrict__ out,
+                                                             float *__restrict__ mse, float *__restrict__ tv) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.x, img = blockIdx.y;
+    trigger_fwd_plane<true>(sm, x + ((long)img * 3 + c) * hw2, noise + (long)img * hw2 * 8, P, k1, rate, hw, c, img,
+                            out + ((long)img * 3 + c) * hw2, nullptr, mse, tv);
 }
 
 // The paired trigger of the input-aware step: 2n workgroup rows over ONE batch of images x [n] and the generator's
@@ -153,19 +182,28 @@ __global__ __launch_bounds__(256) void trigger_pair_fwd_kernel(const float *__re
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int hw2 = hw * hw, c = blockIdx.x, row = blockIdx.y;
     const int cross = row >= n, img = cross ? row - n : row;
-    trigger_fwd_plane(sm, x + ((long)img * 3 + c) * hw2, noise + (long)row * hw2 * 8, P, k1 + 3 * cross, rate, hw, c,
-                      img, (cross ? out_cross : out_bd) + ((long)img * 3 + c) * hw2, nullptr, cross ? nullptr : mse);
+    trigger_fwd_plane<false>(sm, x + ((long)img * 3 + c) * hw2, noise + (long)row * hw2 * 8, P, k1 + 3 * cross, rate, hw,
+                             c, img, (cross ? out_cross : out_bd) + ((long)img * 3 + c) * hw2, nullptr,
+                             cross ? nullptr : mse, nullptr);
 }
 
 // d_noise = rate * P * ( clampmask .* (Kb^T * (d_out + 2*l2*(out-x)) * Kb) ) * P      (P symmetric)
 // LDS (floats): Pl, Pr, A, B as above + G [hw][hw]
 // The per-(channel, image) body, shared by trigger_bwd_kernel and trigger_pair_bwd_kernel: xi / nz / dn are the
 // image's plane of x, noise pixels and gradient pixels (c8); d_out, d_out2, outp point at its plane of channel c.
+// TV (train_generator_imperceptible.py:228, :234-237): the gradient of tv_scale * TV(out) joins g before the blur
+// adjoint.  d|a - b| = sgn(a - b) with sgn(0) = 0, so pixel (y, x) collects
+//   sgn(o[y][x] - o[y-1][x]) - sgn(o[y+1][x] - o[y][x]) + sgn(o[y][x] - o[y][x-1]) - sgn(o[y][x+1] - o[y][x]),
+// terms past the border absent.  The out plane is staged in B (free until the first product writes it), so the five
+// reads per pixel are unit-stride LDS reads; g without the term is computed by the same instructions as without TV.
+__device__ __forceinline__ float sgnf(float d) { return (float)((d > 0.f) - (d < 0.f)); }
+
+template <bool TV>
 __device__ __forceinline__ void trigger_bwd_plane(float *sm, const float *__restrict__ xi, const __bf16 *__restrict__ nz,
                                                   const float *__restrict__ P, const float *__restrict__ k1, float rate,
                                                   int hw, int c, const float *__restrict__ d_out,
                                                   const float *__restrict__ d_out2, const float *__restrict__ outp,
-                                                  float l2_scale, int pre_tanh, __bf16 *__restrict__ dn) {
+                                                  float l2_scale, float tv_scale, int pre_tanh, __bf16 *__restrict__ dn) {
     const int hw2 = hw * hw, lp = hw + 1, tid = threadIdx.x;
     float *Pl = sm, *Pr = Pl + hw * lp, *A = Pr + hw2, *B = A + hw2, *G = B + hw * lp;
     const float kk[3] = {k1[0], k1[1], k1[2]};
@@ -178,8 +216,22 @@ __device__ __forceinline__ void trigger_bwd_plane(float *sm, const float *__rest
         if (d_out2) g += d_out2[o];      // a second gradient of the same tensor (another classifier's share)
         if (l2_scale != 0.f) g = fmaf(2.f * l2_scale, outp[o] - xi[o], g);
         G[o] = g;
+        if (TV) B[o] = outp[o];
     }
     __syncthreads();
+    if (TV) {
+        for (int o = tid; o < hw2; o += 256) {
+            const int y = o / hw, xx = o - y * hw;
+            const float v = B[o];
+            float s = 0.f;
+            if (y > 0) s += sgnf(v - B[o - hw]);
+            if (y + 1 < hw) s -= sgnf(B[o + hw] - v);
+            if (xx > 0) s += sgnf(v - B[o - 1]);
+            if (xx + 1 < hw) s -= sgnf(B[o + 1] - v);
+            G[o] = fmaf(tv_scale, s, G[o]);
+        }
+        __syncthreads();
+    }
     mm4(Pl, lp, A, B, lp, hw, tid);
     __syncthreads();
     mm4(B, lp, Pr, A, hw, hw, tid);              // A = P N P  (pre-clamp value is x + rate*A)
@@ -221,9 +273,24 @@ __global__ __launch_bounds__(256) void trigger_bwd_kernel(const float *__restric
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int hw2 = hw * hw, c = blockIdx.x, img = blockIdx.y;
     const long pl = ((long)img * 3 + c) * hw2;
-    trigger_bwd_plane(sm, x + pl, noise + (long)img * hw2 * 8, P, k1, rate, hw, c, d_out ? d_out + pl : nullptr,
-                      d_out2 ? d_out2 + pl : nullptr, outp ? outp + pl : nullptr, l2_scale, pre_tanh,
-                      d_noise + (long)img * hw2 * 8);
+    trigger_bwd_plane<false>(sm, x + pl, noise + (long)img * hw2 * 8, P, k1, rate, hw, c, d_out ? d_out + pl : nullptr,
+                             d_out2 ? d_out2 + pl : nullptr, outp ? outp + pl : nullptr, l2_scale, 0.f, pre_tanh,
+                             d_noise + (long)img * hw2 * 8);
+}
+
+// trigger_bwd_kernel + tv_scale * d TV(out) / d out in the image gradient (outp is required).
+__global__ __launch_bounds__(256) void trigger_tv_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                             const float *__restrict__ P, const float *__restrict__ k1,
+                                                             float rate, int hw, const float *__restrict__ d_out,
+                                                             const float *__restrict__ d_out2,
+                                                             const float *__restrict__ outp, float l2_scale,
+                                                             float tv_scale, int pre_tanh, __bf16 *__restrict__ d_noise) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.x, img = blockIdx.y;
+    const long pl = ((long)img * 3 + c) * hw2;
+    trigger_bwd_plane<true>(sm, x + pl, noise + (long)img * hw2 * 8, P, k1, rate, hw, c, d_out ? d_out + pl : nullptr,
+                            d_out2 ? d_out2 + pl : nullptr, outp + pl, l2_scale, tv_scale, pre_tanh,
+                            d_noise + (long)img * hw2 * 8);
 }
 
 // Backward of trigger_pair_fwd_kernel, one launch over 2n workgroup rows.  Row i < n: the gradient of noise[i] from
@@ -241,9 +308,9 @@ __global__ __launch_bounds__(256) void trigger_pair_bwd_kernel(const float *__re
     const int cross = row >= n, img = cross ? row - n : row;
     const long pl = ((long)img * 3 + c) * hw2;
     const float *g1 = cross ? d_cross : d_bd, *g2 = cross ? nullptr : d_bd2;
-    trigger_bwd_plane(sm, x + pl, noise + (long)row * hw2 * 8, P, k1 + 3 * cross, rate, hw, c, g1 ? g1 + pl : nullptr,
-                      g2 ? g2 + pl : nullptr, cross || !out_bd ? nullptr : out_bd + pl, cross ? 0.f : l2_scale, pre_tanh,
-                      d_noise + (long)row * hw2 * 8);
+    trigger_bwd_plane<false>(sm, x + pl, noise + (long)row * hw2 * 8, P, k1 + 3 * cross, rate, hw, c,
+                             g1 ? g1 + pl : nullptr, g2 ? g2 + pl : nullptr, cross || !out_bd ? nullptr : out_bd + pl,
+                             cross ? 0.f : l2_scale, 0.f, pre_tanh, d_noise + (long)row * hw2 * 8);
 }
 
 // ------------------------------------------------------------------ augmentation
@@ -537,6 +604,39 @@ extern "C" int combat_trigger_bwd(const float *x, const void *noise, const float
     COMBAT_LAUNCH(trigger_bwd_kernel, dim3(3, n), dim3(256), bytes, as_stream(stream), x,
                        reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, d_out, d_out2, out, l2_scale,
                        pre_tanh, reinterpret_cast<__bf16 *>(d_noise));
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+
+extern "C" int combat_trigger_tv_fwd(const float *x, const void *noise, const float *P, const float *k1,
+                                     float noise_rate, int32_t n, int32_t hw, float *out, float *mse_partial,
+                                     float *tv_partial, void *stream) {
+    COMBAT_PLAN_HOOK(combat_trigger_tv_fwd, x, noise, P, k1, noise_rate, n, hw, out, mse_partial, tv_partial);
+    if (!x || !noise || !P || !k1 || !out || !tv_partial || n < 0 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (n == 0) return COMBAT_OK;
+    const int bytes = (4 * hw * hw + 2 * hw) * 4;
+    if (set_smem(trigger_tv_fwd_kernel, bytes)) return COMBAT_ELAUNCH;
+    COMBAT_LAUNCH(trigger_tv_fwd_kernel, dim3(3, n), dim3(256), bytes, as_stream(stream), x,
+                       reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, out, mse_partial, tv_partial);
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+
+extern "C" int combat_trigger_tv_bwd(const float *x, const void *noise, const float *P, const float *k1,
+                                     float noise_rate, int32_t n, int32_t hw, const float *d_out, const float *d_out2,
+                                     const float *out, float l2_scale, float tv_scale, int32_t pre_tanh, void *d_noise,
+                                     void *stream) {
+    if (tv_scale == 0.f)      // nothing to add: the launch of combat_trigger_bwd itself
+        return combat_trigger_bwd(x, noise, P, k1, noise_rate, n, hw, d_out, d_out2, out, l2_scale, pre_tanh, d_noise, stream);
+    COMBAT_PLAN_HOOK(combat_trigger_tv_bwd, x, noise, P, k1, noise_rate, n, hw, d_out, d_out2, out, l2_scale, tv_scale,
+                     pre_tanh, d_noise);
+    if (!x || !noise || !P || !k1 || !out || !d_noise || n < 0 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (n == 0) return COMBAT_OK;
+    const int bytes = (5 * hw * hw + 2 * hw) * 4;
+    if (set_smem(trigger_tv_bwd_kernel, bytes)) return COMBAT_ELAUNCH;
+    COMBAT_LAUNCH(trigger_tv_bwd_kernel, dim3(3, n), dim3(256), bytes, as_stream(stream), x,
+                       reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, d_out, d_out2, out, l2_scale,
+                       tv_scale, pre_tanh, reinterpret_cast<__bf16 *>(d_noise));
     CB_LAUNCH_CHECK();
     return COMBAT_OK;
 }

@@ -878,6 +878,73 @@ class InputAwareStep(AlternatedStep):
                     sCe.bufs[k].zero_()
 
 
+class ImperceptibleStep(AlternatedStep):
+    """The alternated step of the reference's imperceptible configuration (train_generator_imperceptible.py:160-277):
+    AlternatedStep with the smoothness of the triggered images in the generator's loss,
+
+        loss = loss_ce + L2_weight * loss_l2 + tv_weight * loss_tv + clean_model_weight * clean_model_loss   (:234-237)
+        loss_tv = total_variation(inputs_bd).mean()                                                           (:228)
+
+    total_variation (kornia 0.6.6) is, per image, the sum over C, H, W of |x[..., 1:, :] - x[..., :-1, :]| plus the same
+    along W.  It is restated in the kernels (combat_trigger_tv_fwd / _bwd), not pinned against kornia.  The per-plane
+    sums come out of the Phase-G trigger launch, the sign stencil of the gradient joins the image gradient inside the
+    trigger backward launch, and the logged sum rides in the log-terms launch: the step's launch count is the parent's.
+    Phase C, the draws' order and the networks are the parent's; like the input-aware script, the reference blurs with
+    the module-level T.GaussianBlur(kernel_size=3, sigma=(0.1, 1)) (:52), whatever --kernel_size / --sigma say.  At
+    tv_weight 0 the trigger backward is the parent's launch, and the step leaves the parent's bits."""
+
+    SIGMA_RANGE = (0.1, 1.0)
+    _PER_N = AlternatedStep._PER_N + ("tv",)
+
+    def __init__(self, netC, netG, clean_model, netF, opt, process_group=None):
+        opt = copy.copy(opt)     # the fixed blur (:52): every blur kernel of the step is built from opt.kernel_size
+        opt.kernel_size = 3
+        super().__init__(netC, netG, clean_model, netF, opt, process_group)
+
+    def _setup(self, n: int):
+        if n == self.N:
+            return
+        cached = n in self._sets
+        super()._setup(n)
+        if not cached:
+            self.tv = torch.empty(3 * n, dtype=f32, device=self.dev)   # per (image, channel) total variation of inputs_bd
+
+    def _draw(self, targets_cpu, bd_targets_cpu) -> StepRandomness:
+        """The parent's order (one sigma per create_inputs_bd call, :172-174 and :203), from the fixed range."""
+        return draw_randomness(targets_cpu, bd_targets_cpu, self.opt, self.transforms, self.SIGMA_RANGE)
+
+    def _trigger_g(self, x_ptr, n, k1g, s2) -> None:
+        """inputs_bd of the whole batch (:203) with its squared-error and total-variation partials."""
+        ops.check(lib.combat_trigger_tv_fwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1g,
+                                            float(self.opt.noise_rate), n, self.hw, self.bd.data_ptr(), self.mse.data_ptr(),
+                                            self.tv.data_ptr(), s2), "trigger tv G")
+
+    def _log_terms(self, n, s2, f_logits) -> None:
+        """The parent's logged terms + loss_tv (:228, :245) -> acc[2]."""
+        ops.check(lib.combat_log_terms_tv(self.inputs.data_ptr(), self.bd.data_ptr(), self.mse.data_ptr(), self.tv.data_ptr(),
+                                          n, self.hw, f_logits.data_ptr() if f_logits is not None else None,
+                                          self.acc.data_ptr(), self.acc_side.data_ptr(), s2), "log terms tv")
+
+    def _gen_backward(self, x_ptr, n, k1g, st, prof) -> None:
+        """The parent's, with tv_weight * d loss_tv / d inputs_bd in the image gradient (:234-239)."""
+        hw = self.hw
+        l2_scale = float(self.opt.L2_weight) / float(n * 3 * hw * hw)
+        tv_scale = float(self.opt.tv_weight) / float(n)                        # .mean() over the batch (:228)
+        ops.check(lib.combat_trigger_tv_bwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1g,
+                                            float(self.opt.noise_rate), n, hw, self.d_bd.data_ptr(), self.d_bd2.data_ptr(),
+                                            self.bd.data_ptr(), l2_scale, tv_scale, 1,
+                                            self.sG.buf("g.z", (n, hw, hw, 8)).data_ptr(), st), "trigger tv bwd")
+        self._backward_allreduce(self.pl["G_b"], self.eG, prof)
+
+    def read_metrics(self, reset: bool = False) -> Dict[str, float]:
+        """AlternatedStep's keys plus loss_tv_sum, the sum of the per-step loss_tv (:245; "TV Loss" = / samples)."""
+        out = super().read_metrics(reset=False)
+        out["loss_tv_sum"] = float(self.acc[2])
+        if reset:
+            self.reset_metrics()
+        return out
+
+
 def _zero_grad(fp, st):
     from .engine import _zero_grad_call
     return _zero_grad_call(fp, st)

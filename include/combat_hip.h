@@ -414,6 +414,25 @@ int combat_trigger_pair_bwd(const float *x, const void *noise, const float *P, c
                             const float *out_bd, float l2_scale, const float *d_cross /* NULL: zero */, int32_t pre_tanh,
                             void *d_noise, void *stream);
 
+/* Trigger of the imperceptible step (train_generator_imperceptible.py:67-75 create_inputs_bd, :228 loss_tv =
+ * kornia.losses.total_variation(inputs_bd).mean(), :234-237 the loss line).  Per image, TV(out) = sum over C, H, W of
+ * |out[y+1][x] - out[y][x]| + |out[y][x+1] - out[y][x]| (kornia 0.6.6; restated, not pinned against kornia itself).
+ * combat_trigger_tv_fwd: combat_trigger_fwd (without src_index / out_c8) + tv_partial fp32 [3n], the per-(image,
+ * channel) share of TV(out), taken from the blurred plane while the workgroup still holds it.  out and mse_partial
+ * carry the bits combat_trigger_fwd writes.
+ * combat_trigger_tv_bwd: combat_trigger_bwd with tv_scale * dTV(out)/d out added to d_out (+ d_out2) + the L2 term,
+ * before the blur adjoint:
+ *   sgn(o[y][x] - o[y-1][x]) - sgn(o[y+1][x] - o[y][x]) + sgn(o[y][x] - o[y][x-1]) - sgn(o[y][x+1] - o[y][x]),
+ * terms past the border absent, sgn(0) = 0 (ATen's abs backward).  `out` is required unless tv_scale == 0, which is
+ * combat_trigger_bwd's launch itself (bit-identical).  For loss_tv's weight w and batch size n: tv_scale = w / n. */
+int combat_trigger_tv_fwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
+                          int32_t n, int32_t hw, float *out, float *mse_partial /* may be NULL */, float *tv_partial,
+                          void *stream);
+int combat_trigger_tv_bwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
+                          int32_t n, int32_t hw, const float *d_out, const float *d_out2 /* NULL, or added to d_out */,
+                          const float *out, float l2_scale, float tv_scale, int32_t pre_tanh, void *d_noise,
+                          void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * PostTensorTransform (utils/dataloader.py:45-60): per-sample crop(pad, integer offset) ->
  * rotation(bilinear, zeros, about the centre) -> horizontal flip, in one gather.
@@ -500,6 +519,11 @@ int combat_colsum(const void *x, int64_t rows, int32_t C, int32_t c_out, float *
  * NULL).  x, xb: fp32 [n][3][hw][hw]; acc2, hits: fp64 device accumulators. */
 int combat_log_terms(const float *x, const float *xb, const float *mse_partial, int32_t n, int32_t hw,
                      const float *detector_logits, double *acc2, double *hits, void *stream);
+/* combat_log_terms + the imperceptible step's logged TV term (train_generator_imperceptible.py:228, :245):
+ * acc3[2] += sum(tv_partial) / n, the batch mean of the per-image total variation, from combat_trigger_tv_fwd's
+ * per-plane sums (fp32 [3n]), added in plane order in every mode.  acc3[0], acc3[1], hits: as combat_log_terms. */
+int combat_log_terms_tv(const float *x, const float *xb, const float *mse_partial, const float *tv_partial, int32_t n,
+                        int32_t hw, const float *detector_logits, double *acc3, double *hits, void *stream);
 /* 2x2 max pool, bf16 NHWC (frequency model.py:21,32,43) */
 int combat_maxpool2(const void *x, int32_t n, int32_t h, int32_t w, int32_t C, void *out, void *stream);
 /* y = BN_eval(ELU(x)) elementwise per channel, bf16 in/out (frequency model.py:14-16) */

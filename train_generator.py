@@ -181,13 +181,18 @@ def detector_checkpoint_path(opt):
     return os.path.join(folder, opt.F_model, name)
 
 
-def main(get_model=None, train=None, eval=None):
-    """``get_model`` / ``train`` / ``eval`` default to this module's; train_generator_wanet.py passes its own."""
+def main(get_model=None, train=None, eval=None, prepare=None, resume_clean_model=True):
+    """``get_model`` / ``train`` / ``eval`` default to this module's; train_generator_wanet.py passes its own.
+    ``prepare(opt)`` runs on the parsed options before anything reads them; ``resume_clean_model=False`` keeps the
+    clean model of --load_checkpoint_clean on --continue_training (train_generator_imperceptible.py:527 and around
+    do not load the checkpoint's copy)."""
     get_model = get_model or globals()["get_model"]
     train = train or globals()["train"]
     eval = eval or globals()["eval"]
     opt = config.get_arguments().parse_args()
     configure_dataset(opt)
+    if prepare is not None:
+        prepare(opt)
     rank, local_rank, world = cdist.init()
     if opt.device == "cuda":
         opt.device = "cuda:%d" % local_rank
@@ -235,7 +240,8 @@ def main(get_model=None, train=None, eval=None):
         netG.load_state_dict(sd["netG"])
         optimizerG.load_state_dict(sd["optimizerG"])
         schedulerG.load_state_dict(sd["schedulerG"])
-        clean_model.load_state_dict(sd["clean_model"])
+        if resume_clean_model:
+            clean_model.load_state_dict(sd["clean_model"])
         api.load_momentum_from_optimizer(optimizerC, netC)
         api.load_momentum_from_optimizer(optimizerG, netG)
         best = [sd[k] for k in ("best_clean_acc", "best_bd_acc", "best_F_acc", "best_clean_model_acc",
