@@ -4,7 +4,15 @@
 
 The shared library exports exactly the C ABI of include/combat_hip.h; it has no torch or
 Python dependency.  Objects are cached under combat_amd/csrc/_obj keyed on source mtimes.
+
+Every link goes to a temporary name first.  tools/check_counted_waits.py disassembles that file's gfx950 code and
+checks the counted vmcnt waits of the DMA-staged convolution kernels against the loads the compiler kept; only a
+library that passed is moved to its final name, so a dropped load fails the build, not a training run, and no later
+build() can find an unchecked library up to date.  The price: while a rebuild links and checks, there is NO library
+under the final name, so build() is not safe to call from several processes at once (ranks of one job, say): build
+once, before the ranks start; a process that only loads the library never triggers a link.
 """
+import importlib.util
 import os
 import subprocess
 import sys
@@ -26,6 +34,20 @@ def _newer(target, deps):
         return True
     t = os.path.getmtime(target)
     return any(os.path.getmtime(d) > t for d in deps)
+
+
+def check_counted_waits(lib=LIB, verbose=True):
+    """Run tools/check_counted_waits.py on the linked library; raises RuntimeError on an error."""
+    spec = importlib.util.spec_from_file_location("check_counted_waits", os.path.join(ROOT, "tools", "check_counted_waits.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    res = mod.check_file(lib)
+    if verbose or not res.ok():
+        print(res.report(), flush=True)
+    if not res.ok():
+        raise RuntimeError("counted-wait check failed: %d error(s), first: %s at 0x%x: %s"
+                           % (len(res.errors), res.errors[0].kernel, res.errors[0].addr, res.errors[0].text))
+    return res
 
 
 def build(force=False, verbose=True):
@@ -50,7 +72,12 @@ def build(force=False, verbose=True):
         with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
             list(ex.map(run, jobs))
     if jobs or force or _newer(LIB, objs):
-        run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs)
+        tmp = LIB + ".unchecked"
+        if os.path.exists(LIB):
+            os.remove(LIB)          # (stale against its objects: never left loadable while the new one is unchecked)
+        run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp] + objs)
+        check_counted_waits(tmp, verbose)       # raises: LIB stays absent, so the next build() links and checks again
+        os.replace(tmp, LIB)
     return LIB
 
 

@@ -44,6 +44,8 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 //   COMBAT_ABL_NODMA   no weight / halo DMA after the first halo patch (the counted waits shrink accordingly)
 //   COMBAT_ABL_NOREAD  no LDS fragment reads (the MFMAs run on whatever the registers hold)
 //   COMBAT_ABL_NOEPI   no epilogue (operand fetches still issued; nothing is stored)
+//   COMBAT_ABL_NOTOUCH no epi_touch() / ws_touch(): the dead operand fetches of a one-flavour kernel are dropped and the
+//                      counted waits go wrong -- never run; tools/check_counted_waits.py must reject such an object
 #if defined(COMBAT_ABL_NODMA)
 #define ABL_DMA(x) 0
 #else
@@ -617,7 +619,9 @@ __device__ __forceinline__ void conv3x3_dma_body(const DmaParams &p) {
         // loads in flight at taps PF_T + 1 / + 2 -- would let the weight tiles of taps 6 / 7 be read before they
         // have landed (seen only with cold caches, inside the step: isolated launches passed 2 800 times).  Every
         // fetched register is therefore "used" here, as in the kernels that carry all flavours.
+#ifndef COMBAT_ABL_NOTOUCH
         if constexpr (FLX >= 0) epi_touch<TE>(epi);
+#endif
         block_barrier();
 #ifdef COMBAT_ABL_NOEPI     // (ablation: one store per lane keeps the accumulators alive)
         {
@@ -972,7 +976,9 @@ __device__ __forceinline__ void conv3x3_ws_body(const DmaParams &p) {
         WS_STAMP(5 + 6 * k);
         const int tm_done = tm_cur;
         const bool more = k + 1 < ng;
+#ifndef COMBAT_ABL_NOTOUCH
         ws_touch(epi);       // (the operand fetches have landed: say so before the DMA below enters the wait counts)
+#endif
         if (more) {          // the patch of this group's next tile lands while the other group computes
             next_tile();
             issue_halo();
