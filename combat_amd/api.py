@@ -65,6 +65,22 @@ def frequency_logits(netF, inputs_bd: torch.Tensor, opt) -> torch.Tensor:
     return slot.bufs["logits"][:n].clone()
 
 
+def pooled_features(netC, inputs: torch.Tensor) -> torch.Tensor:
+    """The eval-mode classifier's pooled features (the input of its `linear`; preact_resnet.py:99-100, resnet.py:93-95)
+    for a float32 NCHW device batch: fp32 [n][in] in torch's NCHW-flatten order, a copy.  It is the pass `netC(inputs)`
+    runs -- same slot, same plan, no launch added -- read one buffer earlier (combat_head_fwd's `pooled` output)."""
+    if netC.training:
+        raise ValueError("pooled_features: the classifier must be in eval mode")
+    from .engine import pad_batch
+    eng = netC._net_engine()
+    eng.refresh()
+    n, _, hw, _ = inputs.shape
+    slot = eng.slot("module.eval", pad_batch(n), hw)
+    ops.image_to_c8(inputs.contiguous().float(), eng.input(slot))
+    eng.forward_plan(slot, False).run()
+    return eng.head_bufs(slot)["pooled"][:n].clone()
+
+
 def sync_momentum_to_optimizer(optimizer, module) -> None:
     """The fused SGD keeps momentum in the engine's flat buffer; mirror it into the torch optimiser's
     state so `optimizer.state_dict()` (checkpoint key optimizerC/optimizerG) has the reference layout."""

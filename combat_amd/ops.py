@@ -347,6 +347,22 @@ def head_bwd(pooled, n, hw, c, weight, logits, targets, loss_weight, dlogits, d_
                               _stream()), "combat_head_bwd", "n=%d hw=%d C=%d" % (n, hw, c))
 
 
+def prune_sweep(pooled, weight, bias, order, per, targets, correct, targets2=None, correct2=None) -> None:
+    """correct[k] (+= , int32 [C]) counts the images whose level-k prediction equals targets (correct2 / targets2
+    likewise): pooled fp32 [n][C * per], order int32 [C] (include/combat_hip.h, combat_prune_sweep)."""
+    n, c = pooled.shape[0], order.numel()
+    check(lib.combat_prune_sweep(pooled.data_ptr(), n, weight.data_ptr(), bias.data_ptr(), order.data_ptr(), c, per,
+                                 weight.shape[0], _p(targets), _p(targets2), _p(correct), _p(correct2), _stream()),
+          "combat_prune_sweep", "n=%d C=%d per=%d classes=%d" % (n, c, per, weight.shape[0]))
+
+
+def feature_colsum(pooled, acc) -> None:
+    """acc (fp64 [in]) += the column sums of pooled (fp32 [n][in]), rows in index order."""
+    n, fin = pooled.shape
+    check(lib.combat_feature_colsum(pooled.data_ptr(), n, fin, acc.data_ptr(), _stream()), "combat_feature_colsum",
+          "n=%d in=%d" % (n, fin))
+
+
 def sgd_nesterov(ptrs, sizes, count, max_size, lr, momentum, weight_decay, grad_scale, first_step) -> None:
     check(lib.combat_sgd_nesterov(ptrs.data_ptr(), sizes.data_ptr(), count, max_size, lr, momentum, weight_decay,
                                   grad_scale, int(first_step), _stream()), "combat_sgd_nesterov", "count=%d" % count)

@@ -480,6 +480,34 @@ int combat_head_bwd_weights(const float *dlogits, const float *pooled, int32_t n
                             int32_t classes, float *dW, float *db, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Fine-pruning defense (defenses/fine_pruning/fine-pruning.py).  The reference sorts layer4's 512 channels by mean
+ * activation over the test set (:144-163) and, for each of the 512 pruning levels, deep-copies the classifier, rebuilds
+ * layer4[1].conv2 and `linear` without the pruned channels (:168-211) and evaluates the whole test set (:213).  Removing
+ * output channel c of that convolution and of the residual (preact_resnet.py:36-37) leaves the surviving channels as they
+ * were, so the pruned network's logits are  b + sum over kept c of W[:, c] . pooled[:, c]  of the UNPRUNED network's
+ * pooled features (the `pooled` output of combat_head_fwd): one forward pass serves every level.
+ *
+ * combat_prune_sweep: pooled fp32 [n][in], W fp32 [classes][in], b [classes], order int32 [C] (the pruning order,
+ * fine-pruning.py:162 seq_sort), in = C * per, feature c * per + q belongs to channel c (torch's NCHW flatten; per = 1 for
+ * a 32 x 32 input, 4 for 64 x 64 -- convert(), :40-50 -- and 49 for 224 x 224).  Level k in [0, C) has channels
+ * order[0 .. k-1] pruned (level 0: the intact network; the reference never prunes all C, :168-173).  Fixed arithmetic:
+ *   s = b[j];  for k = C-1 down to 0, for q = 0 .. per-1:  s = fmaf(pooled[i][order[k]*per + q], W[j][order[k]*per + q], s)
+ * and s after channel order[k] is the level-k logit of image i, class j (a fresh ordered sum of the kept channels for
+ * every level, not a running subtraction); prediction = the first maximal class (torch.argmax, :70, :79).
+ *   correct[k]  += #{i : pred_k(i) == targets[i]}     int32 [C]
+ *   correct2[k] += #{i : pred_k(i) == targets2[i]}    (targets2 and correct2: both NULL, or both given)
+ * accumulated INTO the arrays with integer atomics, so the batches of a test set add up and every run gives the same
+ * bits in every mode.  COMBAT_EINVAL for classes > 16, C < 1, per not in {1, 4, 49}, n < 0; n == 0 is a no-op.
+ *
+ * combat_feature_colsum: acc[f] += sum_i pooled[i][f] (acc fp64 [in], rows added in index order, no atomics): the mean of
+ * layer4's output over [0, 2, 3] (:161) is the mean of `pooled` over the images and the `per` cells of a channel.
+ * ------------------------------------------------------------------------------------------ */
+int combat_prune_sweep(const float *pooled, int32_t n, const float *W, const float *b, const int32_t *order, int32_t C,
+                       int32_t per, int32_t classes, const int64_t *targets, const int64_t *targets2, int32_t *correct,
+                       int32_t *correct2, void *stream);
+int combat_feature_colsum(const float *pooled, int32_t n, int32_t in, double *acc, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * SGD(momentum, weight_decay, nesterov) over a list of tensors (train_generator.py:123,125,212,255;
  * torch.optim.SGD semantics: g += wd*p; buf = first ? g : mu*buf + g; p -= lr*(g + mu*buf)).
  * ptrs: DEVICE array of 3*count pointers (param, grad, buf triples); sizes: DEVICE int64[count].
