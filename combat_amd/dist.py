@@ -28,18 +28,25 @@ def limit_host_threads() -> None:
 
 
 def init(backend: Optional[str] = None) -> Tuple[int, int, int]:
-    """(rank, local_rank, world) from the torchrun environment; no-op for a single process."""
+    """(rank, local_rank, world) from the torchrun environment; no-op for a single process.
+
+    COMBAT_DIST_BACKEND=gloo (as in bench.py): rehearsal of the multi-rank path on a box with fewer GPUs than ranks --
+    RCCL refuses two ranks on one device, so the exchange goes over gloo and the ranks share the devices there are
+    (the returned local_rank is the device index: LOCAL_RANK modulo the device count)."""
     limit_host_threads()
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank, local = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     if world > 1 and not dist.is_initialized():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29500")
-        backend = backend or ("nccl" if torch.cuda.is_available() else "gloo")
+        backend = backend or os.environ.get("COMBAT_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")
         if backend == "nccl":
             torch.cuda.set_device(local)
             dist.init_process_group(backend, device_id=torch.device("cuda", local))
         else:
+            if torch.cuda.is_available():
+                local %= torch.cuda.device_count()
+                torch.cuda.set_device(local)
             dist.init_process_group(backend)
     return rank, local, world
 

@@ -855,7 +855,7 @@ class InputAwareStep(AlternatedStep):
         self._gen_bwd[0].run(prof)
         grad.add_(self._g_cross)
         if self.world > 1 or (FORCE_ALLREDUCE and self.pg is not None):
-            torch.distributed.all_reduce(grad, group=self.pg)   # one flat all-reduce (the multi-rank path is untested)
+            torch.distributed.all_reduce(grad, group=self.pg)   # one flat all-reduce
 
     # ---- metrics
     def read_metrics(self, reset: bool = False) -> Dict[str, float]:

@@ -3,7 +3,15 @@
 Launched as `python -m torch.distributed.run --nproc-per-node 2 tests/dp_rehearsal.py OUT` with
 COMBAT_DIST_BACKEND=gloo: two ranks share the one GPU of the box (RCCL refuses two ranks on one device; the
 exchange goes over gloo, everything else -- plans, marks, bucketed all-reduce launches, auxiliary-stream
-joins, optimiser scaling -- is the code path of an 8-GPU run).  Every rank writes OUT/rank<r>.json."""
+joins, optimiser scaling -- is the code path of an 8-GPU run).  Every rank writes OUT/rank<r>.json.
+
+`gen_grad_check` is the reference for the REDUCED GENERATOR gradient, shared with tests/dp_rehearsal_attacks.py.  Phase G
+runs behind netC's optimiser step, and the data-parallel netC (mean gradient) differs from a single rank's, so a
+single-rank generator gradient is no reference -- unless Phase C runs at lr_c = 0.0: `p - 0 * (...)` leaves netC's
+parameters as they were (BatchNorm running statistics still move, but they are rank-local by design), every rank enters
+Phase G with the netC, draws and images of its single-process run, and
+
+    eG.fp.grad after the data-parallel step == single-rank eG.fp.grad of rank 0 + single-rank eG.fp.grad of rank 1."""
 import json
 import os
 import sys
@@ -39,6 +47,76 @@ def rel(a, b):
     return float((a - b).norm() / max(float(b.norm()), 1e-30))
 
 
+def gather(buf, world):
+    """CPU copies of every rank's `buf` (gloo)."""
+    got = [torch.zeros_like(buf).cpu() for _ in range(world)]
+    dist.all_gather(got, buf.detach().cpu().contiguous())
+    return got
+
+
+def aug_table(n, rng):
+    """One augmentation table ([n, 4]: crop dx, dy, angle in radians, flip -- combat_amd/augment.py) with every
+    transform active, from a rank's own numpy generator."""
+    out = np.zeros((n, 4), np.float32)
+    out[:, 0:2] = rng.integers(-5, 6, (n, 2))
+    out[:, 2] = np.where(rng.random(n) < 0.5, (rng.random(n) * 2 - 1) * 10.0, 0.0) * (np.pi / 180.0)
+    out[:, 3] = rng.random(n) < 0.5
+    return out
+
+
+UNET_UPDATE_KEYS = ("conv0_0.weight", "conv3_1.weight", "upconv2_0.weight", "upconv0_0.weight")   # first down conv,
+#                                                                           innermost block, an up conv, last conv
+
+
+def gen_grad_check(res, tag, make, run, world, lr_g, keys=UNET_UPDATE_KEYS):
+    """The reduced generator gradient of one step class against the sum of the ranks' single-process gradients, at
+    lr_c = 0.0 (module docstring).  make(process_group) -> a step object over freshly built networks (same seeds on
+    every call and rank); run(st, lr_c) -> this rank's first step (own shard, own draws) at the step's default lr_g,
+    which the caller states as `lr_g`.  Writes into `res`:
+      <tag>_gradG_sum_vs_singles   rel(g_dp, s0 + s1)           over GridEngine.head_grad_range() for the WaNet head
+      <tag>_gradG_vs_own           rel(g_dp, s_own)             ~1: the exchange added something
+      <tag>_gradG_singles_differ   rel(s0, s1)                  ~1: the two shards are distinct
+      <tag>_noise                  rel of two single-rank runs from the same state (atomics reorder sums)
+      <tag>_netC_unchanged         netC's flat parameters equal before / after every one of the three steps
+      <tag>_paramG_update_vs_mean_grad   four generator tensors against p0 - lr_g * (1 + mu) * (mean_g + wd * p0)
+      <tag>_paramG_update_vs_sum_grad    the same against the SUM of the singles (recorded, not a reference)
+    Returns this rank's single-process netC gradient (of the same first step: Phase C's gradient does not depend on lr_c)."""
+    def first_step(pg):
+        st = make(pg)
+        st.keep_grads = True
+        c0 = st.eC.fp.flat.detach().clone()
+        p0 = {k: v.detach().clone() for k, v in st.netG.named_parameters() if k in keys}
+        run(st, 0.0)
+        torch.cuda.synchronize()
+        lo, hi = st.eG.head_grad_range() if hasattr(st.eG, "head_grad_range") else (0, st.eG.fp.total)
+        return st, (lo, hi), p0, bool(torch.equal(st.eC.fp.flat, c0))
+
+    st, (lo, hi), _, same_a = first_step(None)
+    s_a, gc_single = st.eG.fp.grad[lo:hi].detach().clone(), st.eC.fp.grad.detach().clone()
+    del st
+    st, _, _, same_b = first_step(None)
+    s_b = st.eG.fp.grad[lo:hi].detach().clone()
+    del st
+    st, _, p0, same_dp = first_step(dist.group.WORLD)
+    g_dp = st.eG.fp.grad[lo:hi].detach().clone()          # the SUM over ranks (the mean is folded into the optimiser)
+    singles = gather(s_a, world)
+    total = singles[0] + singles[1]
+    res[tag + "_gradG_sum_vs_singles"] = rel(g_dp.cpu(), total)
+    res[tag + "_gradG_vs_own"] = rel(g_dp, s_a)
+    res[tag + "_gradG_singles_differ"] = rel(singles[0], singles[1])
+    res[tag + "_noise"] = rel(s_b, s_a)
+    res[tag + "_netC_unchanged"] = same_a and same_b and same_dp
+    fp = st.eG.fp
+    mean = torch.zeros_like(fp.grad)
+    mean[lo:hi] = total.cuda() * 0.5
+    now = dict(st.netG.named_parameters())
+    update = lambda scale: max(
+        rel(now[k].detach(), p0[k] - lr_g * 1.9 * (fp.logical(mean, k) * scale + 5e-4 * p0[k])) for k in keys)
+    res[tag + "_paramG_update_vs_mean_grad"] = update(1.0)
+    res[tag + "_paramG_update_vs_sum_grad"] = update(2.0)     # (recorded: what an optimiser that applied the SUM would show)
+    return gc_single
+
+
 def main():
     out_dir = sys.argv[1]
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
@@ -54,18 +132,18 @@ def main():
            step_mod.StepRandomness(1, 0.6, 0.5 + 0.2 * rank, [None] * 5)]
     res = {}
 
-    # ---- single-rank run of this rank's first step from the common start state (no process group)
-    netc, netg, clean, netf = build(nets)
-    p0 = {k: v.detach().clone() for k, v in netc.named_parameters()}
-    st1 = step_mod.AlternatedStep(netc, netg, clean, netf, Opt())
-    st1.keep_grads = True
-    st1.run(x.cuda(), t, rnd[0])
-    torch.cuda.synchronize()
-    g_single = st1.eC.fp.grad.detach().clone()
-    del st1, netc, netg, clean, netf
+    # ---- the reduced generator gradient at lr_c = 0.0 (gen_grad_check); its single-rank run of this rank's first step
+    # from the common start state (no process group) is also the reference of netC's reduced gradient below
+    def make_alt(pg):
+        netc, netg, clean, netf = build(nets)
+        return step_mod.AlternatedStep(netc, netg, clean, netf, Opt(), process_group=pg)
+
+    g_single = gen_grad_check(res, "alternated", make_alt, lambda s, lr_c: s.run(x.cuda(), t, rnd[0], lr_c=lr_c), world,
+                              Opt.lr_G)
 
     # ---- the data-parallel run: 2 steps
     netc, netg, clean, netf = build(nets)
+    p0 = {k: v.detach().clone() for k, v in netc.named_parameters()}
     st = step_mod.AlternatedStep(netc, netg, clean, netf, Opt(), process_group=dist.group.WORLD)
     st.keep_grads = True
     st.run(x.cuda(), t, rnd[0])
@@ -143,15 +221,21 @@ def main():
         res[tag + "_replicas_bit_identical_after_2_steps"] = gather_equal(sd.eC.fp.flat) and gather_equal(sd.eC.fp.mom)
         del sd, netc, netg
 
-    torch.manual_seed(0)
-    netc = nets.PreActResNet18().cuda()
-    torch.manual_seed(1)
-    clean = nets.PreActResNet18().cuda().eval()
-    torch.manual_seed(2)
-    netg = nets.GridGenerator(WOpt()).cuda()
-    torch.manual_seed(3)
-    netf = nets.FrequencyModel(2, 3, 32).cuda().eval()
-    sw = step_mod.WanetStep(netc, netg, clean, netf, WOpt(), process_group=dist.group.WORLD)
+    def make_wanet(pg):
+        torch.manual_seed(0)
+        netc = nets.PreActResNet18().cuda()
+        torch.manual_seed(1)
+        clean = nets.PreActResNet18().cuda().eval()
+        torch.manual_seed(2)
+        netg = nets.GridGenerator(WOpt()).cuda()
+        torch.manual_seed(3)
+        netf = nets.FrequencyModel(2, 3, 32).cuda().eval()
+        return step_mod.WanetStep(netc, netg, clean, netf, WOpt(), process_group=pg)
+
+    # the grid head's reduced gradient by VALUE (head_grad_range); conv0_0.weight only sees the weight decay
+    gen_grad_check(res, "wanet", make_wanet, lambda s, lr_c: s.run(x.cuda(), t, rnd[0], lr_c=lr_c), world, WOpt.lr_G,
+                   keys=("fc1.bias", "fc2.weight", "fc2.bias", "conv0_0.weight"))
+    sw = make_wanet(dist.group.WORLD)
     sw.keep_grads = True
     sw.run(x.cuda(), t, rnd[0])
     torch.cuda.synchronize()

@@ -155,6 +155,42 @@ def test_wanet_imagenet10_workflow_on_synthetic_data(tmp_path):
     assert all(torch.isfinite(v.float()).all() for v in sd["netC"].values())
 
 
+def _two_rank_rehearsal(worker, out_dir):
+    """Start `worker` as two fresh rank processes on this box's one GPU (exchange over gloo) and return both ranks'
+    result JSON.  One child, no retry; a non-zero exit fails with the tail of its output."""
+    import json
+    import socket
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.join(ROOT, "tests", worker), str(out_dir)]
+    env = dict(os.environ, PYTHONPATH=ROOT, COMBAT_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-3000:]
+    return [json.load(open(out_dir / ("rank%d.json" % rank))) for rank in (0, 1)]
+
+
+def _assert_reduced_generator_gradient(res, tag):
+    """tests/dp_rehearsal.py::gen_grad_check: at lr_c = 0.0 netC stays what it was (the precondition that makes a
+    single-process run a reference for Phase G), the reduced generator gradient is the sum of the two ranks'
+    single-process gradients (the bound of the same identity on netC: fp32 atomics in some weight-gradient launches
+    reorder sums) and not this rank's own (100 x the bound: the exchange added the other shard, and the shards
+    differ), and the optimiser applied their mean.  The repeat noise of the reference is recorded beside it.
+
+    Measured on the MI355X (rel. L2; error of the sum / repeat noise of a single-process run): alternated 5.5e-8 /
+    4.7e-8 .. 5.5e-8, input-aware 4.2e-8 / 3.3e-8 .. 3.9e-8, imperceptible 3.8e-8 / 3.2e-8 .. 3.5e-8, WaNet head 0 / 0
+    (its backward has no atomics); in the library's deterministic mode all of them are exactly 0.  Against this rank's
+    own gradient 0.61 .. 1.65, between the two singles 1.2 .. 1.4.  Update against the mean 4e-11 .. 2.3e-9; the same
+    tensors against the SUM of the singles 9e-6 (input-aware, lr_g 1e-3) .. 2e-4."""
+    print(tag, {k: v for k, v in res.items() if k.startswith(tag + "_")})
+    assert res[tag + "_netC_unchanged"] is True, (tag, res)
+    assert res[tag + "_noise"] >= 0.0, (tag, res)
+    assert res[tag + "_gradG_sum_vs_singles"] < 1e-5, (tag, res)
+    assert res[tag + "_gradG_vs_own"] > 1e-3 and res[tag + "_gradG_singles_differ"] > 1e-3, (tag, res)
+    assert res[tag + "_paramG_update_vs_mean_grad"] < 1e-6, (tag, res)
+
+
 def test_data_parallel_step_two_ranks_one_gpu(tmp_path):
     """SURVEY 8(e) without an 8-GPU node: two fresh rank processes share this box's GPU and exchange over gloo
     (tests/dp_rehearsal.py).  After step 1 the all-reduced netC gradient is the sum of the two single-rank
@@ -162,19 +198,10 @@ def test_data_parallel_step_two_ranks_one_gpu(tmp_path):
     applied their MEAN; netG's reduced gradient is the same bits on both ranks; after 2 steps parameters and
     momentum of both trained networks are bit-identical replicas.  The same for ClassifierStep (train_victim.py behind
     a UNet, train_victim_wanet.py behind a GridGenerator, train_clean_classifier.py) and WanetStep, whose all-reduces
-    take other routes (plan marks of the victim's backward; the grid head's gradient range)."""
-    import json
-    import socket
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "tests", "dp_rehearsal.py"), str(tmp_path)]
-    env = dict(os.environ, PYTHONPATH=ROOT, COMBAT_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-3000:]
-    for rank in (0, 1):
-        res = json.load(open(tmp_path / ("rank%d.json" % rank)))
+    take other routes (plan marks of the victim's backward; the grid head's gradient range).  For AlternatedStep and
+    WanetStep the reduced GENERATOR gradient is also checked by value (_assert_reduced_generator_gradient).
+    10.7 s on the MI355X."""
+    for res in _two_rank_rehearsal("dp_rehearsal.py", tmp_path):
         assert res["gradC_sum_vs_singles"] < 1e-5, res
         assert res["paramC_update_vs_mean_grad"] < 1e-6, res
         assert res["gradG_identical_across_ranks"] and res["replicas_bit_identical_after_2_steps"] and res["finite"], res
@@ -185,6 +212,31 @@ def test_data_parallel_step_two_ranks_one_gpu(tmp_path):
         assert res["wanet_head_grad_identical_across_ranks"] and res["wanet_head_grad_nonzero"], res
         assert res["wanet_grad_outside_head_range_is_zero"] and res["wanet_gradC_identical_across_ranks"], res
         assert res["wanet_replicas_bit_identical_after_2_steps"], res
+        # the reduced GENERATOR gradient by value (UNet: the whole flat buffer; WaNet: the grid head's range)
+        for tag in ("alternated", "wanet"):
+            _assert_reduced_generator_gradient(res, tag)
+
+
+def test_data_parallel_attack_steps_two_ranks_one_gpu(tmp_path):
+    """InputAwareStep and ImperceptibleStep on two ranks (tests/dp_rehearsal_attacks.py; b = 16 per rank, own images,
+    second batch, labels and draws per rank).  Per class: the reduced generator gradient against the sum of the
+    single-process gradients at lr_c = 0.0 -- for the input-aware step that covers the cross half reaching the
+    exchange, the `_g_cross` add ordered before the one flat all-reduce and the all-reduce ordered behind both
+    backward plans and their auxiliary streams; for the imperceptible step that tv_weight / n per rank with
+    grad_scale = 1 / world is the mean over the global batch --, netC's reduced gradient and update at the default
+    lr_c, and a second step with one poisoned image on rank 0 and none on rank 1 after which both networks'
+    parameters and momentum are the same bits on both ranks.
+    Measured: netC's reduced gradient against the sum of the singles 5.9e-8 (both classes), its update against the mean
+    6.3e-9 / 6.9e-9; cross loss sum 4.6, TV loss sum 3.3e3 over the two steps.  9.6 s on the MI355X (the worker of
+    test_data_parallel_step_two_ranks_one_gpu: 10.7 s)."""
+    for res in _two_rank_rehearsal("dp_rehearsal_attacks.py", tmp_path):
+        for tag, own_sum in (("inputaware", "loss_cross_sum"), ("imperceptible", "loss_tv_sum")):
+            _assert_reduced_generator_gradient(res, tag)
+            assert res[tag + "_gradC_sum_vs_singles"] < 1e-5, (tag, res)
+            assert res[tag + "_paramC_update_vs_mean_grad"] < 1e-6, (tag, res)
+            assert res[tag + "_replicas_bit_identical_after_unequal_step"] is True, (tag, res)
+            assert res[tag + "_finite"] is True and res[tag + "_samples"] == 32, (tag, res)
+            assert res[tag + "_" + own_sum] > 0, (tag, res)
 
 
 def test_rccl_streams_beside_the_step_on_one_gpu():

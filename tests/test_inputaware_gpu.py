@@ -323,3 +323,41 @@ def test_inputaware_workflow_on_synthetic_data(tmp_path):
     vic = os.path.join(cwd, "ckpt", "victim_ia_clean", "cifar10", "cifar10_victim_ia_clean.pth.tar")
     assert set(torch.load(vic, map_location="cpu", weights_only=True)) == {
         "netC", "schedulerC", "optimizerC", "netG", "best_clean_acc", "best_bd_acc", "best_cross_acc", "epoch_current"}
+
+
+def test_inputaware_script_on_two_ranks(tmp_path):
+    """train_generator_inputaware.py under torch.distributed.run with two ranks on this box's one GPU (exchange over
+    gloo, as tests/test_entrypoints_gpu.py's rehearsal): two sharded train loaders per rank (100 of 200 images each:
+    batches of 64 and 36), the evaluation loaders' shards ending in a 36-image batch, the counters summed and
+    the BatchNorm statistics averaged over the ranks, and rank 0 alone writing the checkpoint.  16 s on the MI355X,
+    the clean classifier's epoch included."""
+    import glob
+    import socket
+    cwd = str(tmp_path)
+    common = ["--synthetic", "--synthetic_size", "200", "--bs", "64", "--checkpoints", os.path.join(cwd, "ckpt"),
+              "--allow_missing_F", "--log_interval", "1", "--n_iters", "1", "--seed", "1"]
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "train_clean_classifier.py"), "--saving_prefix", "classifier_clean"]
+                       + common, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-3000:]
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), "--log-dir", os.path.join(cwd, "ranks"), "--tee", "3",
+           os.path.join(ROOT, "train_generator_inputaware.py"), "--saving_prefix", "inputaware", "--load_checkpoint_clean",
+           "classifier_clean"] + common
+    env = dict(env, COMBAT_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    r = subprocess.run(cmd, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-3000:]
+    logs = glob.glob(os.path.join(cwd, "ranks", "**", "stdout.log"), recursive=True)
+    rank0 = [f for f in logs if os.path.basename(os.path.dirname(f)) == "0"]
+    assert len(logs) == 2 and len(rank0) == 1, logs
+    out0 = open(rank0[0]).read()
+    assert "Cross Acc:" in out0 and "Saving..." in out0, out0[-3000:]
+    written = glob.glob(os.path.join(cwd, "ckpt", "inputaware_clean", "**", "*.pth.tar"), recursive=True)
+    assert written == [os.path.join(cwd, "ckpt", "inputaware_clean", "cifar10", "cifar10_inputaware_clean.pth.tar")], written
+    sd = torch.load(written[0], map_location="cpu", weights_only=True)
+    assert set(sd) == GEN_KEYS
+    for net in ("netC", "netG"):
+        assert all(torch.isfinite(v.float()).all() for v in sd[net].values()), net

@@ -16,7 +16,8 @@ train_generator.py's.  What differs, and is added here:
 The per-batch body (:170-290) runs as ``combat_amd.step.InputAwareStep`` on the HIP kernels.
 
 Data parallel: ``python -m torch.distributed.run --nproc-per-node N ...`` shards BOTH train loaders like the first
-(combat_amd.dist).  That path has not been run on more than one GPU.
+(combat_amd.dist).  Run with two ranks on one GPU over gloo (COMBAT_DIST_BACKEND=gloo: tests/test_inputaware_gpu.py);
+not run over RCCL on several GPUs.
 """
 import os
 import random
