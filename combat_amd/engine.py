@@ -316,6 +316,23 @@ def _aux_pointers(parent: torch.cuda.Stream, n: int):
     return arr
 
 
+_HIP = None
+
+
+def low_priority_stream(dev) -> torch.cuda.Stream:
+    """A stream of the LOWEST priority the device offers (torch only exposes normal / high)."""
+    global _HIP
+    if _HIP is None:
+        _HIP = ctypes.CDLL("libamdhip64.so")
+    least, greatest = ctypes.c_int(), ctypes.c_int()
+    assert _HIP.hipDeviceGetStreamPriorityRange(ctypes.byref(least), ctypes.byref(greatest)) == 0
+    h = ctypes.c_void_p()
+    with torch.cuda.device(dev):
+        assert _HIP.hipStreamCreateWithPriority(ctypes.byref(h), 1, least.value) == 0      # 1 = hipStreamNonBlocking
+    print("low-priority stream: range least %d greatest %d" % (least.value, greatest.value), flush=True)
+    return torch.cuda.ExternalStream(h.value, device=dev)
+
+
 def _aux_stream(parent: torch.cuda.Stream, k: int = 0) -> torch.cuda.Stream:
     """The auxiliary stream of the stream a plan runs on, for calls marked aux (weight gradients beside
     the input-gradient chain).  Per parent stream: two chains that run concurrently must not order each
@@ -326,7 +343,6 @@ def _aux_stream(parent: torch.cuda.Stream, k: int = 0) -> torch.cuda.Stream:
     s = _AUX_STREAMS.get(key)
     if s is None:
         if os.environ.get("COMBAT_LOW_PRIO_SIDE", "0") == "1":
-            from .step import low_priority_stream
             s = low_priority_stream(parent.device)
         else:
             s = torch.cuda.Stream(device=parent.device)

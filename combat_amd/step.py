@@ -19,6 +19,7 @@ import contextlib
 import copy
 import math
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import os
@@ -30,7 +31,8 @@ from . import ops, trigger
 from ._lib import lib
 from .augment import PostTensorTransform
 from .dist import GradReducer, bucket_ranges
-from .engine import FreqEngine, PlanSeq, PreActEngine, UnetEngine, f32, short_workgroups
+from .engine import (FreqEngine, PlanSeq, PreActEngine, UnetEngine, _zero_grad_call, f32, low_priority_stream,
+                     short_workgroups)
 
 BUCKETS = (8, 16, 32, 64, 128, 256, 512, 1024)
 
@@ -63,12 +65,17 @@ def create_targets_bd(targets: torch.Tensor, opt) -> torch.Tensor:
     raise Exception("{} attack mode is not implemented".format(opt.attack_mode))
 
 
+def draw_num_bd(targets_cpu: torch.Tensor, bd_targets_cpu: torch.Tensor, pc: float) -> int:
+    """How many of the batch's target-class images are poisoned (train_generator.py:183; numpy global RNG)."""
+    n_trg = int((targets_cpu == bd_targets_cpu).sum())
+    return int(np.sum(np.random.rand(n_trg) < pc))
+
+
 def draw_randomness(targets_cpu: torch.Tensor, bd_targets_cpu: torch.Tensor, opt, transforms: PostTensorTransform,
                     sigma_range=(0.1, 1.0)) -> StepRandomness:
     """Consume the three RNG streams exactly where the reference does."""
     n = targets_cpu.shape[0]
-    n_trg = int((targets_cpu == bd_targets_cpu).sum())
-    num_bd = int(np.sum(np.random.rand(n_trg) < opt.pc))                 # :183
+    num_bd = draw_num_bd(targets_cpu, bd_targets_cpu, opt.pc)           # :183
     sigma_c = trigger.sample_sigma(sigma_range) if num_bd else 0.5      # :194 (skipped when empty)
     aug0 = transforms.sample(n)                                         # :196
     aug1 = transforms.sample(n)                                         # :214
@@ -86,18 +93,22 @@ def poison_tables(targets: torch.Tensor, bd_targets: torch.Tensor, num_bd: int):
       idx_small    int32 [n]  first num_bd entries = images handed to the generator
       idx_total    int32 [n]  gather indices into the [inputs ; triggered images] staging buffer
                                (rows < num_bd read the triggered copies at n + i)"""
-    n = targets.shape[0]
-    trg = (targets == bd_targets).nonzero()[:, 0]
-    ntrg = (targets != bd_targets).nonzero()[:, 0]
-    perm = torch.cat([trg, ntrg]).to(torch.int32)
+    perm, idx_small, idx_total = order_tables((targets == bd_targets).nonzero()[:, 0], (targets != bd_targets).nonzero()[:, 0], num_bd)
     total_targets = targets[perm.long()].clone()
     total_targets[:num_bd] = bd_targets[perm[:num_bd].long()]
+    return perm, total_targets, idx_small, idx_total
+
+
+def order_tables(first: torch.Tensor, rest: torch.Tensor, num_bd: int):
+    """perm, idx_small and idx_total (see poison_tables) of the batch order [first ; rest] whose first num_bd rows are poisoned."""
+    perm = torch.cat([first, rest]).to(torch.int32)
+    n = perm.shape[0]
     idx_small = torch.zeros(n, dtype=torch.int32)
     idx_small[:num_bd] = perm[:num_bd]
     idx_total = perm.clone()
     if num_bd:
         idx_total[:num_bd] = torch.arange(n, n + num_bd, dtype=torch.int32)
-    return perm, total_targets, idx_small, idx_total
+    return perm, idx_small, idx_total
 
 
 _STREAMS: Dict = {}
@@ -118,23 +129,6 @@ def shared_stream(device, kind: str, priority: int = 0) -> torch.cuda.Stream:
 
 
 LOW_PRIO_SIDE = os.environ.get("COMBAT_LOW_PRIO_SIDE", "0") == "1"   # experiment: second / auxiliary queues below the critical one
-_HIP = None
-
-
-def low_priority_stream(dev) -> torch.cuda.Stream:
-    """A stream of the LOWEST priority the device offers (torch only exposes normal / high)."""
-    import ctypes
-    global _HIP
-    if _HIP is None:
-        _HIP = ctypes.CDLL("libamdhip64.so")
-    least, greatest = ctypes.c_int(), ctypes.c_int()
-    assert _HIP.hipDeviceGetStreamPriorityRange(ctypes.byref(least), ctypes.byref(greatest)) == 0
-    h = ctypes.c_void_p()
-    with torch.cuda.device(dev):
-        assert _HIP.hipStreamCreateWithPriority(ctypes.byref(h), 1, least.value) == 0      # 1 = hipStreamNonBlocking
-    print("low-priority stream: range least %d greatest %d" % (least.value, greatest.value), flush=True)
-    return torch.cuda.ExternalStream(h.value, device=dev)
-
 
 SIDE_SHORT_WORKGROUPS = os.environ.get("COMBAT_SIDE_WS", "0") != "1"   # (COMBAT_SIDE_WS=1: A/B, the persistent kernel on the second stream too)
 # COMBAT_MERGE_C_EVAL=1 (A/B, VERDICT r3 item 5): netC's two eval-mode forwards of Phase G (train_generator.py:227-228) as ONE 2n-image
@@ -176,15 +170,68 @@ def backward_allreduce(plan, eng, pg, world: int, reducers: dict, prof=None) -> 
     reducer.wait()
 
 
-class AlternatedStep:
+# Label rows of the step table (int64 [n] each).  The heads' label buffers are views of these rows, bound where the
+# slots are made; AlternatedStep._run and InputAwareStep._fill_table_extra fill them.
+LAB_TARGETS, LAB_BD, LAB_TOTAL = 0, 1, 2   # targets, bd_targets, total_targets (labels of Phase C's re-ordered batch)
+LAB_K = slice(3, 5)       # the clean model's 2n batch [aug(inputs) ; aug(inputs_bd)]: targets twice
+LAB_K2 = slice(5, 7)      # its second label set: the metric half's row is unused, the loss half's holds bd_targets
+LAB_CROSS = slice(7, 9)   # input-aware only, netC's two-half pass [aug3(bd) ; aug5(bd2)]: bd_targets, targets
+
+
+def step_table(n: int, n_aug: int, n_blur: int, n_lab: int, **alloc):
+    """The step's ONE host->device table (one copy instead of a dozen 10-us ones in front of the generator forward) as
+    zeroed bytes and its typed views: [n_aug augmentation tables | index_small, index_total | n_blur 3-tap blur kernels |
+    n_lab label rows] -> (raw, float32 [n_aug, n, 4], int32 [2, n], float32 [n_blur, 3], int64 [n_lab, n]).  The blur
+    section holds the kernels in pairs of 24 bytes (an odd count leaves 12 bytes of padding), which keeps the label
+    rows 8-byte aligned.  `alloc` goes to torch.zeros (device=..., pin_memory=True)."""
+    o1 = n_aug * n * 16
+    o2 = o1 + 2 * n * 4
+    o3 = o2 + 24 * ((n_blur + 1) // 2)
+    raw = torch.zeros(o3 + n_lab * n * 8, dtype=torch.uint8, **alloc)
+    return (raw, raw[:o1].view(f32).view(n_aug, n, 4), raw[o1:o2].view(torch.int32).view(2, n),
+            raw[o2:o2 + 12 * n_blur].view(f32).view(n_blur, 3), raw[o3:].view(torch.int64).view(n_lab, n))
+
+
+class PerBatchSize:
+    """Buffers, slots and plans of a step are per batch size and cached, one object each (`_build_set`), in `_sets`: the
+    ragged last batch of an epoch (80 images for CIFAR-10) gets its own set once, and the metric cells of every set
+    survive until `read_metrics` sums them.  `cur` is the set of the batch size `N` that ran last."""
+
+    N = 0
+    cur = None
+
+    def _setup(self, n: int):
+        if n != self.N:
+            if n not in self._sets:
+                self._sets[n] = self._build_set(n)
+            self.cur, self.N = self._sets[n], n
+        return self.cur
+
+    def __getattr__(self, name):
+        """Readers outside the step (bench.py, the training scripts, tests, tools) spell a field of the current set as an
+        attribute of the step: `st.bd`, `st.sG`, `st.pl`.  (Only reached when the normal lookup misses; the step itself
+        reads the set.)"""
+        if self.cur is None or not hasattr(self.cur, name):
+            raise AttributeError("%s has no attribute %r" % (type(self).__name__, name))
+        return getattr(self.cur, name)
+
+
+class AlternatedStep(PerBatchSize):
     """Owns the engines, slots and small device tables of one rank's step."""
 
     serial = False   # True: no second stream (bench.py's instrumented replay times one kernel at a time)
     keep_grads = False   # True: leave the flat gradient buffers as the step computed them (tests inspect them);
     #                      default: they are zeroed behind each optimiser step, off the critical queue
     kStage = 4   # pinned staging sets (host steps in flight before it has to wait for the device)
+    TABLE = (5, 2, 7)   # augmentation tables, blur kernels (sigma_c, sigma_g) and label rows of the step table
+    FIXED_BLUR = False   # True: the blur is the reference script's module-level GaussianBlur -- kernel 3, sigma in
+    #                      (0.1, 1) -- whatever --kernel_size / --sigma say
+    CAN_MERGE_C = True   # COMBAT_MERGE_C_EVAL applies (to this class alone: the subclasses lay netC's eval passes out themselves)
 
     def __init__(self, netC, netG, clean_model, netF, opt, process_group=None):
+        if self.FIXED_BLUR:
+            opt = copy.copy(opt)     # every blur kernel of the step is built from opt.kernel_size
+            opt.kernel_size = 3
         self.opt = opt
         self.dev = next(netC.parameters()).device
         self.eC: PreActEngine = netC._net_engine()
@@ -197,7 +244,6 @@ class AlternatedStep:
         if self.world > 1 or (FORCE_ALLREDUCE and process_group is not None):
             self.eC.flush_at_marks = self.eG.flush_at_marks = True    # gradients above an all-reduce mark must be final there
         self.hw = opt.input_height
-        self.N = 0
         dev = self.dev
         self.P = trigger.lowpass_matrix(self.hw, opt.ratio).to(dev)
         self.D = trigger.dct_matrix(self.hw).float().to(dev)
@@ -210,114 +256,95 @@ class AlternatedStep:
         self.steps_done = 0
         self.samples = 0                 # images since the last metric reset
         self._reducers = {}
-        self._sets: Dict[int, dict] = {}
+        self._sets: Dict[int, SimpleNamespace] = {}
+
+    @property
+    def sigma_range(self):
+        return (0.1, 1.0) if self.FIXED_BLUR else getattr(self.opt, "sigma", (0.1, 1.0))
 
     # ------------------------------------------------------------------ buffers per batch size
-    _PER_N = ("inputs", "cat_src", "bd", "d_bd", "d_bd2", "mse", "tab", "tab_f", "tab_i", "k1", "_stage", "_stage_i",
-              "d_targets", "sC_train", "sC_eval", "sC_met", "sC_bd", "sK_eval", "sK_bd", "sG", "sF", "pl",
-              )
-
-    def _setup(self, n: int):
-        """Buffers, slots and plans are per batch size and cached: the ragged last batch of an epoch
-        (80 images for CIFAR-10) gets its own set once and the metric counters of every set survive."""
-        if n == self.N:
-            return
-        if self.N:
-            self._sets[self.N] = {k: getattr(self, k) for k in self._PER_N}
-        if n in self._sets:
-            for k, v in self._sets[n].items():
-                setattr(self, k, v)
-            self.N = n
-            return
-        self.N, dev, hw = n, self.dev, self.hw
-        self.cat_src = torch.zeros(2 * n, 3, hw, hw, dtype=f32, device=dev)   # [inputs ; poisoned images]
-        self.inputs = self.cat_src[:n]
-        self.bd = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)
-        self.d_bd = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)
-        self.d_bd2 = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)   # clean-model share (second stream)
-        self.mse = torch.empty(3 * n, dtype=f32, device=dev)   # per (image, channel)
-        # ONE host->device table per step (one copy instead of a dozen 10-us ones in front of the generator
-        # forward): [5 aug tables | index_small, index_total | blur kernels of sigma_c, sigma_g | label rows].
-        # Label rows: 0 targets, 1 bd_targets, 2 total_targets (re-ordered batch), 3-4 targets twice (the clean
-        # model's 2n batch), 5-6 its second label set (row 6 = bd_targets); the heads' label buffers are
-        # views of these rows.
-        self.tab = torch.zeros(self._table_bytes(n), dtype=torch.uint8, device=dev)
-        self.tab_f, self.tab_i, self.k1, self.d_targets = self._table_views(self.tab, n)
+    def _build_set(self, n: int) -> SimpleNamespace:
+        """The set of one batch size; a subclass adds its own fields to what this returns."""
+        dev, hw = self.dev, self.hw
+        s = SimpleNamespace(n=n)
+        s.cat_src = torch.zeros(2 * n, 3, hw, hw, dtype=f32, device=dev)   # [inputs ; poisoned images]
+        s.inputs = s.cat_src[:n]
+        s.bd = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)
+        s.d_bd = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)
+        s.d_bd2 = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)   # clean-model share (second stream)
+        s.mse = torch.empty(3 * n, dtype=f32, device=dev)   # per (image, channel)
+        s.tab, s.tab_f, s.tab_i, s.k1, s.d_targets = step_table(n, *self.TABLE, device=dev)
         # pinned staging, a ring of kStage sets: the host runs several steps ahead of the device, and an
         # asynchronous copy reads its pinned source when the DEVICE gets to it -- a set is rewritten only
         # after the event behind its last copy has completed
-        self._stage = []
+        s._stage = []
         for _ in range(self.kStage):
-            raw = torch.zeros(self._table_bytes(n), dtype=torch.uint8).pin_memory()
-            tf, ti, k1, tg = self._table_views(raw, n)
-            self._stage.append(dict(raw=raw, tab_f=tf, tab_i=ti, k1=k1, targets=tg, done=None))
-        self._stage_i = 0
-        eC, eK, eG = self.eC, self.eK, self.eG
+            raw, tf, ti, k1, tg = step_table(n, *self.TABLE, pin_memory=True)
+            s._stage.append(dict(raw=raw, tab_f=tf, tab_i=ti, k1=k1, targets=tg, done=None))
+        s._stage_i = 0
+        eC, eK = self.eC, self.eK
         # The eval-mode forwards of one network are independent per sample.  clean_model (off the critical
         # path, second stream): the metric-only forward and the differentiated one run as ONE 2n-image batch
         # [aug(inputs) ; aug(inputs_bd)] (train_generator.py:214+250 -- clean_model is frozen and :214
         # reads only `inputs`, so running it in Phase G changes nothing), backward on the triggered half
         # through a view slot.  netC (:227+228): the differentiated forward is on the critical path and runs
         # alone; the accuracy-only forward on the clean images goes to the second stream.
-        self.sC_train = eC.slot("C.train", n, hw)
-        self.merge_c = MERGE_C_EVAL and type(self) is AlternatedStep
-        self._c_eval_slots(n)
-        self.sK_eval = eK.slot("K.eval2", 2 * n, hw)
-        self.sG = self._gen_slot(n)
-        self.sF = self.eF.slot("F", n, hw) if self.eF is not None else None
-        # the heads read their labels straight out of the step table (bound before the plans marshal pointers)
-        lab = self.d_targets
-        self._c_eval_labels(lab)
-        self.sK_eval.bufs["targets"], self.sK_eval.bufs["targets2"] = lab[3:5].view(-1), lab[5:7].view(-1)
+        # The heads read their labels straight out of the step table (bound before the plans marshal pointers).
+        lab = s.d_targets
+        s.sC_train = eC.slot("C.train", n, hw)
+        s.sC_train.bufs["targets"] = lab[LAB_TOTAL]
+        s.merge_c = MERGE_C_EVAL and self.CAN_MERGE_C
+        self._c_eval_slots(s)
+        s.sK_eval = eK.slot("K.eval2", 2 * n, hw)
+        s.sK_eval.bufs["targets"], s.sK_eval.bufs["targets2"] = lab[LAB_K].view(-1), lab[LAB_K2].view(-1)
+        s.sG = self._gen_slot(n)
+        s.sF = self.eF.slot("F", n, hw) if self.eF is not None else None
         w_cm = float(self.opt.clean_model_weight)
         # one head launch per differentiated pass (forward + feature gradient: combat_head_fwd_bwd), where the engine has it
         hb = FUSED_HEAD and type(eC) is PreActEngine
-        self.pl = dict(
-            C_train_f=eC.forward_plan(self.sC_train, True, **(dict(head_bwd=True) if hb else {})),
-            C_train_b=eC.backward_train_plan(self.sC_train, **(dict(head_done=True) if hb else {})),
-            C_eval_f=self._c_eval_fwd_plan(hb),
+        s.pl = dict(
+            C_train_f=eC.forward_plan(s.sC_train, True, **(dict(head_bwd=True) if hb else {})),
+            C_train_b=eC.backward_train_plan(s.sC_train, **(dict(head_done=True) if hb else {})),
+            C_eval_f=self._c_eval_fwd_plan(s, hb),
         )
-        self.pl.update(self._gen_plans())
-        self.sC_bd, self.pl["C_bd_b"] = self._c_eval_bwd_plan(n, hb)
+        s.pl.update(self._gen_plans(s))
+        s.sC_bd, s.pl["C_bd_b"] = self._c_eval_bwd_plan(s, hb)
         # the second stream's passes run beside the critical queue: one tile per workgroup (engine.short_workgroups)
         with (short_workgroups() if SIDE_SHORT_WORKGROUPS else contextlib.nullcontext()):
-            if not self.merge_c:
-                self.pl["C_met_f"] = eC.forward_plan(self.sC_met, False, 1.0, False)
-            self.pl["K_eval_f"] = eK.forward_plan(self.sK_eval, False, w_cm, True, split_head=True)
-            self.sK_bd = self.sK_eval.half_view(n, n, eK.FWD_SHARED)
-            self.pl["K_bd_b"] = eK.backward_eval_plan(self.sK_bd, w_cm)
-            if self.sF is not None:
-                self.pl["F_f"] = self.eF.forward_plan(self.sF)
+            if not s.merge_c:
+                s.pl["C_met_f"] = eC.forward_plan(s.sC_met, False, 1.0, False)
+            s.pl["K_eval_f"] = eK.forward_plan(s.sK_eval, False, w_cm, True, split_head=True)
+            s.sK_bd = s.sK_eval.half_view(n, n, eK.FWD_SHARED)
+            s.pl["K_bd_b"] = eK.backward_eval_plan(s.sK_bd, w_cm)
+            if s.sF is not None:
+                s.pl["F_f"] = self.eF.forward_plan(s.sF)
+        return s
 
-    # ---- netC's eval-mode passes of Phase G (train_generator.py:227-231): slots, labels, forward, input-gradient backward
-    def _c_eval_slots(self, n) -> None:
-        eC, hw = self.eC, self.hw
-        if self.merge_c:
-            self.sC_eval = eC.slot("C.eval2", 2 * n, hw)   # [metric half ; loss half]
-            self.sC_met = self.sC_eval
+    # ---- netC's eval-mode passes of Phase G (train_generator.py:227-231): slots with their labels, forward, input-gradient backward
+    def _c_eval_slots(self, s) -> None:
+        eC, hw, n, lab = self.eC, self.hw, s.n, s.d_targets
+        if s.merge_c:
+            s.sC_eval = eC.slot("C.eval2", 2 * n, hw)   # [metric half ; loss half]
+            s.sC_met = s.sC_eval
+            s.sC_eval.bufs["targets"] = lab[LAB_TARGETS:LAB_BD + 1].view(-1)
         else:
-            self.sC_eval = eC.slot("C.evalbd", n, hw)      # netC on the triggered images: on the critical path, so on its own
-            self.sC_met = eC.slot("C.metric", n, hw)       # netC on the clean images (accuracy only): second stream
+            s.sC_eval = eC.slot("C.evalbd", n, hw)      # netC on the triggered images: on the critical path, so on its own
+            s.sC_met = eC.slot("C.metric", n, hw)       # netC on the clean images (accuracy only): second stream
+            s.sC_eval.bufs["targets"], s.sC_met.bufs["targets"] = lab[LAB_BD], lab[LAB_TARGETS]
 
-    def _c_eval_labels(self, lab) -> None:
-        if self.merge_c:
-            self.sC_train.bufs["targets"], self.sC_eval.bufs["targets"] = lab[2], lab[0:2].view(-1)
-        else:
-            self.sC_train.bufs["targets"], self.sC_eval.bufs["targets"], self.sC_met.bufs["targets"] = lab[2], lab[1], lab[0]
+    def _c_eval_fwd_plan(self, s, hb):
+        return self.eC.forward_plan(s.sC_eval, False, 1.0, False,
+                                    **(dict(split_head=True) if s.merge_c else dict(head_bwd=True) if hb else {}))
 
-    def _c_eval_fwd_plan(self, hb):
-        return self.eC.forward_plan(self.sC_eval, False, 1.0, False,
-                                    **(dict(split_head=True) if self.merge_c else dict(head_bwd=True) if hb else {}))
-
-    def _c_eval_bwd_plan(self, n, hb):
+    def _c_eval_bwd_plan(self, s, hb):
         eC = self.eC
-        sbd = self.sC_eval.half_view(n, n, eC.FWD_SHARED) if self.merge_c else self.sC_eval
-        return sbd, eC.backward_eval_plan(sbd, 1.0, **(dict(head_done=True) if hb and not self.merge_c else {}))
+        sbd = s.sC_eval.half_view(s.n, s.n, eC.FWD_SHARED) if s.merge_c else s.sC_eval
+        return sbd, eC.backward_eval_plan(sbd, 1.0, **(dict(head_done=True) if hb and not s.merge_c else {}))
 
     def _c_eval_inputs(self, x_ptr, bd_ptr, xC, aug_ptr, n, st) -> None:
         """The augmented images of netC's differentiated eval pass (:228; merged: + :227)."""
         hw = self.hw
-        if self.merge_c:
+        if self.cur.merge_c:
             ops.check(lib.combat_augment_fwd(x_ptr, None, aug_ptr[2], n, hw, xC.data_ptr(), None, st), "augment 2")
             ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[3], n, hw, xC[n:].data_ptr(), None, st), "augment 3")
         else:
@@ -325,8 +352,9 @@ class AlternatedStep:
 
     def _c_eval_grads(self, aug_ptr, n, st) -> None:
         """Image gradient of that pass through the augmentation -> d_bd."""
-        ops.check(lib.combat_augment_bwd(self.sC_bd.bufs["g.img"].data_ptr(), 8, aug_ptr[3], n, self.hw,
-                                         self.d_bd.data_ptr(), 0, st), "augment 3 bwd")
+        s = self.cur
+        ops.check(lib.combat_augment_bwd(s.sC_bd.bufs["g.img"].data_ptr(), 8, aug_ptr[3], n, self.hw,
+                                         s.d_bd.data_ptr(), 0, st), "augment 3 bwd")
 
     def _fill_table_extra(self, hs, rnd, targets_cpu, bd_targets_cpu) -> None:
         """Entries of the step table a subclass adds (staging set `hs`, before its copy)."""
@@ -334,20 +362,8 @@ class AlternatedStep:
     def _gen_slot(self, n):
         return self.eG.slot("G", n, self.hw)
 
-    def _gen_plans(self) -> dict:
-        return dict(G_f=self.eG.forward_plan(self.sG), G_b=self.eG.backward_plan(self.sG))
-
-    @staticmethod
-    def _table_bytes(n: int) -> int:
-        return 5 * n * 16 + 2 * n * 4 + 24 + 7 * n * 8
-
-    @staticmethod
-    def _table_views(raw: torch.Tensor, n: int):
-        o1 = 5 * n * 16
-        o2 = o1 + 2 * n * 4
-        o3 = o2 + 24
-        return (raw[:o1].view(f32).view(5, n, 4), raw[o1:o2].view(torch.int32).view(2, n),
-                raw[o2:o3].view(f32).view(2, 3), raw[o3:].view(torch.int64).view(7, n))
+    def _gen_plans(self, s) -> dict:
+        return dict(G_f=self.eG.forward_plan(s.sG), G_b=self.eG.backward_plan(s.sG))
 
     def _side_stream(self) -> torch.cuda.Stream:
         if self.serial:            # kernel-level measurements: everything in line on the caller's stream
@@ -382,7 +398,7 @@ class AlternatedStep:
     def _run(self, inputs, targets_cpu, rnd, lr_c, lr_g, prof) -> None:
         opt = self.opt
         n = inputs.shape[0]
-        self._setup(n)
+        s = self._setup(n)
         hw, st = self.hw, torch.cuda.current_stream().cuda_stream
         targets_cpu = targets_cpu.cpu()
         bd_targets_cpu = create_targets_bd(targets_cpu, opt).cpu()
@@ -391,24 +407,23 @@ class AlternatedStep:
         nb = rnd.num_bd
         # ---- host tables (train_generator.py:181-204: batch order [poisoned, rest of target class, others])
         perm, tot, idx_small, idx_total = poison_tables(targets_cpu, bd_targets_cpu, nb)
-        hs = self._stage[self._stage_i]
-        self._stage_i = (self._stage_i + 1) % self.kStage
+        hs = s._stage[s._stage_i]
+        s._stage_i = (s._stage_i + 1) % self.kStage
         if hs["done"] is not None:
             hs["done"].synchronize()       # (only ever waits if the device is kStage steps behind)
         h_targets, h_tab_i, h_tab_f, h_k1 = hs["targets"], hs["tab_i"], hs["tab_f"], hs["k1"]
-        h_targets[0].copy_(targets_cpu)
-        h_targets[1].copy_(bd_targets_cpu)
-        h_targets[2].copy_(tot)
-        h_targets[3].copy_(targets_cpu)
-        h_targets[4].copy_(targets_cpu)
-        h_targets[6].copy_(bd_targets_cpu)
+        h_targets[LAB_TARGETS].copy_(targets_cpu)
+        h_targets[LAB_BD].copy_(bd_targets_cpu)
+        h_targets[LAB_TOTAL].copy_(tot)
+        h_targets[LAB_K].copy_(targets_cpu)        # (both rows)
+        h_targets[LAB_K2][1].copy_(bd_targets_cpu)
         h_tab_i[0].copy_(idx_small)
         h_tab_i[1].copy_(idx_total)
         aug_ptr = []
         for i, a in enumerate(rnd.aug):
             if a is not None:
                 h_tab_f[i].copy_(torch.from_numpy(a))
-            aug_ptr.append(self.tab_f[i].data_ptr() if a is not None else None)
+            aug_ptr.append(s.tab_f[i].data_ptr() if a is not None else None)
         h_k1[0].copy_(torch.from_numpy(trigger.gaussian_kernel1d(rnd.sigma_c, opt.kernel_size)))
         h_k1[1].copy_(torch.from_numpy(trigger.gaussian_kernel1d(rnd.sigma_g, opt.kernel_size)))
         self._fill_table_extra(hs, rnd, targets_cpu, bd_targets_cpu)
@@ -416,15 +431,15 @@ class AlternatedStep:
         # mapping), batch, and the generator's re-packed output bias
         extra = self.eG.small_refresh_copy() if hasattr(self.eG, "small_refresh_copy") else None
         direct = inputs.dtype == f32 and inputs.is_contiguous() and (inputs.is_cuda or inputs.is_pinned()) and \
-            tuple(inputs.shape) == tuple(self.inputs.shape)
+            tuple(inputs.shape) == tuple(s.inputs.shape)
         if os.environ.get("COMBAT_NO_COPY3") == "1":          # A/B: three asynchronous copies
-            self.tab.copy_(hs["raw"], non_blocking=True)
+            s.tab.copy_(hs["raw"], non_blocking=True)
             direct = False
             if extra:
                 self.eG.bias8_taken = False
         else:
-            ops.check(lib.combat_copy3(self.tab.data_ptr(), hs["raw"].data_ptr(), hs["raw"].numel(),
-                                       self.inputs.data_ptr() if direct else None, inputs.data_ptr() if direct else None,
+            ops.check(lib.combat_copy3(s.tab.data_ptr(), hs["raw"].data_ptr(), hs["raw"].numel(),
+                                       s.inputs.data_ptr() if direct else None, inputs.data_ptr() if direct else None,
                                        inputs.numel() * 4 if direct else 0,
                                        extra[0] if extra else None, extra[1] if extra else None, extra[2] if extra else 0, st),
                       "combat_copy3")
@@ -435,12 +450,12 @@ class AlternatedStep:
         # staging set until `done` has completed, so a caller may drop its pinned tensor right after run()
         hs["inputs_ref"] = inputs if direct and not inputs.is_cuda else None
         if not direct:
-            self.inputs.copy_(inputs, non_blocking=True)
-        eC, eG, eK, eF, pl = self.eC, self.eG, self.eK, self.eF, self.pl
+            s.inputs.copy_(inputs, non_blocking=True)
+        eC, eG, eK, eF, pl = self.eC, self.eG, self.eK, self.eF, s.pl
         for e in (eC, eG, eK) + ((eF,) if eF is not None else ()):
             e.refresh()
-        k1c, k1g = self.k1[0].data_ptr(), self.k1[1].data_ptr()
-        x_ptr = self.inputs.data_ptr()
+        k1c, k1g = s.k1[0].data_ptr(), s.k1[1].data_ptr()
+        x_ptr = s.inputs.data_ptr()
 
         # ---- generator forward of the whole batch, ONCE for both phases.  The reference runs netG twice
         # (train_generator.py:187 on the poisoned images in eval mode, :216 on the batch in train mode);
@@ -453,8 +468,8 @@ class AlternatedStep:
         # ================= Phase C (train_generator.py:175-212) =================
         if nb:   # the poisoned images: rows index_small[:nb] of the batch and of the generator output (:186-194)
             self._trigger_c(x_ptr, nb, k1c, st)
-        ops.check(lib.combat_augment_fwd(self.cat_src.data_ptr(), self.tab_i[1].data_ptr(), aug_ptr[0], n, hw,
-                                         eC.input(self.sC_train).data_ptr(), None, st), "augment 0")
+        ops.check(lib.combat_augment_fwd(s.cat_src.data_ptr(), s.tab_i[1].data_ptr(), aug_ptr[0], n, hw,
+                                         eC.input(s.sC_train).data_ptr(), None, st), "augment 0")
         pl["C_train_f"].run(prof)
         # ---- fork (enqueued after the surrogate forward so that the main queue is never short of work while the
         # host feeds the second stream).  Everything Phase G does with the clean model and the detector depends only on the
@@ -465,8 +480,8 @@ class AlternatedStep:
         # before it reads the poisoned images and for `ev_side` before the generator backward.
         side = self._side_stream()
         side.wait_event(ev_fork)
-        xK, xC = eK.input(self.sK_eval), eC.input(self.sC_eval)     # [2n, ...]: metric half, loss half / [n, ...]: loss images
-        bd_ptr = self.bd.data_ptr()
+        xK, xC = eK.input(s.sK_eval), eC.input(s.sC_eval)     # [2n, ...]: metric half, loss half / [n, ...]: loss images
+        bd_ptr = s.bd.data_ptr()
         with torch.cuda.stream(side):
             s2 = side.cuda_stream
             self._trigger_g(x_ptr, n, k1g, s2)                                                    # :224-226
@@ -476,8 +491,8 @@ class AlternatedStep:
             ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[4], n, hw, xK[n:].data_ptr(), None, s2), "augment 4")
             pl["K_eval_f"].run(prof)               # :214 (metric half) + :250-251 (loss half)
             pl["K_bd_b"].run(prof)
-            ops.check(lib.combat_augment_bwd(self.sK_bd.bufs["g.img"].data_ptr(), 8, aug_ptr[4], n, hw,
-                                             self.d_bd2.data_ptr(), 0, s2), "augment 4 bwd")
+            ops.check(lib.combat_augment_bwd(s.sK_bd.bufs["g.img"].data_ptr(), 8, aug_ptr[4], n, hw,
+                                             s.d_bd2.data_ptr(), 0, s2), "augment 4 bwd")
             ev_side = torch.cuda.Event()
             ev_side.record()
 
@@ -503,14 +518,14 @@ class AlternatedStep:
         with torch.cuda.stream(side):
             side.wait_event(ev_late)
             s2 = side.cuda_stream
-            if not self.merge_c:
-                ops.check(lib.combat_augment_fwd(x_ptr, None, aug_ptr[2], n, hw, eC.input(self.sC_met).data_ptr(), None, s2),
+            if not s.merge_c:
+                ops.check(lib.combat_augment_fwd(x_ptr, None, aug_ptr[2], n, hw, eC.input(s.sC_met).data_ptr(), None, s2),
                           "augment 2")
                 pl["C_met_f"].run(prof)
             if eF is not None:
-                ops.check(lib.combat_dct_u8(bd_ptr, self.D.data_ptr(), n, hw, eF.input(self.sF).data_ptr(), s2), "dct")
+                ops.check(lib.combat_dct_u8(bd_ptr, self.D.data_ptr(), n, hw, eF.input(s.sF).data_ptr(), s2), "dct")
                 pl["F_f"].run(prof)
-            self._log_terms(n, s2, self.sF.bufs["logits"] if eF is not None else None)
+            self._log_terms(n, s2, s.sF.bufs["logits"] if eF is not None else None)
             ev_met = torch.cuda.Event()
             ev_met.record()
         torch.cuda.current_stream().wait_event(ev_side)     # ---- join
@@ -526,38 +541,42 @@ class AlternatedStep:
 
     # ------------------------------------------------------------------ trigger-specific pieces (UNet + low-pass / clamp-mix / blur)
     def _draw(self, targets_cpu, bd_targets_cpu) -> StepRandomness:
-        return draw_randomness(targets_cpu, bd_targets_cpu, self.opt, self.transforms, getattr(self.opt, "sigma", (0.1, 1.0)))
+        return draw_randomness(targets_cpu, bd_targets_cpu, self.opt, self.transforms, self.sigma_range)
 
     def _gen_forward(self, x_ptr, n, st, prof) -> None:
-        ops.check(lib.combat_image_to_c8(x_ptr, n, self.hw, self.eG.input(self.sG).data_ptr(), st), "c8 G")
-        self.pl["G_f"].run(prof)
+        s = self.cur
+        ops.check(lib.combat_image_to_c8(x_ptr, n, self.hw, self.eG.input(s.sG).data_ptr(), st), "c8 G")
+        s.pl["G_f"].run(prof)
 
     def _trigger_c(self, x_ptr, nb, k1c, st) -> None:
         """Poisoned images of Phase C -> cat_src[n:] (train_generator.py:186-194)."""
-        ops.check(lib.combat_trigger_fwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1c, float(self.opt.noise_rate),
-                                         nb, self.hw, self.tab_i[0].data_ptr(), self.cat_src[self.N:].data_ptr(), None, None, st),
+        s = self.cur
+        ops.check(lib.combat_trigger_fwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1c, float(self.opt.noise_rate),
+                                         nb, self.hw, s.tab_i[0].data_ptr(), s.cat_src[s.n:].data_ptr(), None, None, st),
                   "trigger C")
 
     def _trigger_g(self, x_ptr, n, k1g, s2) -> None:
         """Triggered copy of the whole batch -> self.bd (+ per-plane squared error) (train_generator.py:224-226)."""
-        ops.check(lib.combat_trigger_fwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1g, float(self.opt.noise_rate),
-                                         n, self.hw, None, self.bd.data_ptr(), None, self.mse.data_ptr(), s2), "trigger G")
+        s = self.cur
+        ops.check(lib.combat_trigger_fwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g, float(self.opt.noise_rate),
+                                         n, self.hw, None, s.bd.data_ptr(), None, s.mse.data_ptr(), s2), "trigger G")
 
     def _log_terms(self, n, s2, f_logits) -> None:
         """loss_l2 / loss_grad_l2 running sums (train_generator.py:234-243; the second is logged only) and the
         detector's hit count (:245-247), in one launch (the ATen spelling of the same is _grad_l2 below: 14 launches)."""
-        ops.check(lib.combat_log_terms(self.inputs.data_ptr(), self.bd.data_ptr(), self.mse.data_ptr(), n, self.hw,
+        s = self.cur
+        ops.check(lib.combat_log_terms(s.inputs.data_ptr(), s.bd.data_ptr(), s.mse.data_ptr(), n, self.hw,
                                        f_logits.data_ptr() if f_logits is not None else None, self.acc.data_ptr(),
                                        self.acc_side.data_ptr(), s2), "log terms")
 
     def _gen_backward(self, x_ptr, n, k1g, st, prof) -> None:
         """Image gradient (d_bd + d_bd2) + the L2 term -> generator parameter gradients (train_generator.py:253-254)."""
-        hw = self.hw
+        s, hw = self.cur, self.hw
         l2_scale = float(self.opt.L2_weight) / float(n * 3 * hw * hw)          # :234, :253
-        ops.check(lib.combat_trigger_bwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1g, float(self.opt.noise_rate),
-                                         n, hw, self.d_bd.data_ptr(), self.d_bd2.data_ptr(), self.bd.data_ptr(), l2_scale, 1,
-                                         self.sG.buf("g.z", (n, hw, hw, 8)).data_ptr(), st), "trigger bwd")   # d_bd + d_bd2
-        self._backward_allreduce(self.pl["G_b"], self.eG, prof)
+        ops.check(lib.combat_trigger_bwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g, float(self.opt.noise_rate),
+                                         n, hw, s.d_bd.data_ptr(), s.d_bd2.data_ptr(), s.bd.data_ptr(), l2_scale, 1,
+                                         s.sG.buf("g.z", (n, hw, hw, 8)).data_ptr(), st), "trigger bwd")   # d_bd + d_bd2
+        self._backward_allreduce(s.pl["G_b"], self.eG, prof)
 
     @staticmethod
     def _grad_l2(x: torch.Tensor, xb: torch.Tensor) -> torch.Tensor:
@@ -571,13 +590,6 @@ class AlternatedStep:
         backward_allreduce(plan, eng, self.pg, self.world, self._reducers, prof)
 
     # ------------------------------------------------------------------ metrics
-    def _slot_sets(self):
-        """(sC_train, sC_eval, sK_eval) of every batch size seen so far."""
-        names = ("sC_train", "sC_eval", "sK_eval", "sC_met")
-        out = [tuple(getattr(self, k) for k in names)] if self.N else []
-        out += [tuple(d[k] for k in names) for n, d in self._sets.items() if n != self.N]
-        return out
-
     def read_metrics(self, reset: bool = False) -> Dict[str, float]:
         """One host sync: the running sums the reference prints each step (:257-290), over every
         batch size run since the last reset."""
@@ -588,8 +600,9 @@ class AlternatedStep:
                "loss_l2_sum": float(acc[0]), "loss_grad_l2_sum": float(acc[1]), "clean_correct": 0, "bd_correct": 0,
                "f_correct": int(self.acc_side.cpu()), "clean_model_correct": 0, "clean_model_bd_ba": 0, "clean_model_bd_asr": 0,
                "train_correct": 0}
-        for sCt, sCe, sKe, sCm in self._slot_sets():
-            cC, cE, kE = self.eC.head_bufs(sCt), self.eC.head_bufs(sCe), self.eK.head_bufs(sKe)
+        for s in self._sets.values():
+            sKe, sCm = s.sK_eval, s.sC_met
+            cC, cE, kE = self.eC.head_bufs(s.sC_train), self.eC.head_bufs(s.sC_eval), self.eK.head_bufs(sKe)
             out["loss_c_sum"] += float(cC["loss"])
             out["loss_ce_sum"] += float(cE["loss"])
             out["clean_model_loss_sum"] += float(kE["loss"]) / w_cm
@@ -607,8 +620,8 @@ class AlternatedStep:
         self.samples = 0
         self.acc.zero_()
         self.acc_side.zero_()
-        for sCt, sCe, sKe, sCm in self._slot_sets():
-            for eng, slot in ((self.eC, sCt), (self.eC, sCe), (self.eK, sKe), (self.eC, sCm)):
+        for s in self._sets.values():
+            for eng, slot in ((self.eC, s.sC_train), (self.eC, s.sC_eval), (self.eK, s.sK_eval), (self.eC, s.sC_met)):
                 h = eng.head_bufs(slot)
                 h["loss"].zero_()
                 h["correct"].zero_()
@@ -625,35 +638,33 @@ class WanetStep(AlternatedStep):
     blur is drawn (the reference's WaNet loop has none), so the torch RNG stream is consumed by the augmentation only."""
 
     WARP_GROUPS = 8     # image ranges of the warp backward (partial sums: deterministic, no atomics)
+    CAN_MERGE_C = False
+
+    def __init__(self, netC, netG, clean_model, netF, opt, process_group=None):
+        super().__init__(netC, netG, clean_model, netF, opt, process_group)
+        self._wpartial = torch.zeros(self.WARP_GROUPS, self.hw, self.hw, 2, dtype=f32, device=self.dev)   # (shared by all batch sizes)
 
     def _draw(self, targets_cpu, bd_targets_cpu) -> StepRandomness:
         """train_generator_wanet.py:148, :159, :182, :203-204, :226: num_bd and five augmentation calls -- no blur."""
-        n = targets_cpu.shape[0]
-        n_trg = int((targets_cpu == bd_targets_cpu).sum())
-        num_bd = int(np.sum(np.random.rand(n_trg) < self.opt.pc))
-        return StepRandomness(num_bd, 0.5, 0.5, [self.transforms.sample(n) for _ in range(5)])
+        num_bd = draw_num_bd(targets_cpu, bd_targets_cpu, self.opt.pc)
+        return StepRandomness(num_bd, 0.5, 0.5, [self.transforms.sample(targets_cpu.shape[0]) for _ in range(5)])
 
     def _gen_slot(self, n):
         return None
 
-    def _gen_plans(self) -> dict:
+    def _gen_plans(self, s) -> dict:
         return {}
-
-    def _setup(self, n: int):
-        super()._setup(n)
-        if getattr(self, "_wpartial_n", 0) != n:
-            self._wpartial = torch.zeros(self.WARP_GROUPS, self.hw, self.hw, 2, dtype=f32, device=self.dev)
-            self._wpartial_n = n
 
     def _gen_forward(self, x_ptr, n, st, prof) -> None:
         self.g = self.eG.forward_grid(self.hw, float(self.opt.grid_rescale), st)
 
     def _trigger_c(self, x_ptr, nb, k1c, st) -> None:
-        ops.check(lib.combat_warp_fwd(x_ptr, self.tab_i[0].data_ptr(), self.g["grid"].data_ptr(), 0, nb, self.hw,
-                                      self.cat_src[self.N:].data_ptr(), st), "warp C")
+        s = self.cur
+        ops.check(lib.combat_warp_fwd(x_ptr, s.tab_i[0].data_ptr(), self.g["grid"].data_ptr(), 0, nb, self.hw,
+                                      s.cat_src[s.n:].data_ptr(), st), "warp C")
 
     def _trigger_g(self, x_ptr, n, k1g, s2) -> None:
-        ops.check(lib.combat_warp_fwd(x_ptr, None, self.g["grid"].data_ptr(), 0, n, self.hw, self.bd.data_ptr(), s2), "warp G")
+        ops.check(lib.combat_warp_fwd(x_ptr, None, self.g["grid"].data_ptr(), 0, n, self.hw, self.cur.bd.data_ptr(), s2), "warp G")
 
     def _log_terms(self, n, s2, f_logits) -> None:
         if f_logits is not None:
@@ -665,9 +676,9 @@ class WanetStep(AlternatedStep):
         self.acc[1] += (e[:, :, 1:] - e[:, :, :-1]).pow(2).mean() + (e[:, :, :, 1:] - e[:, :, :, :-1]).pow(2).mean()
 
     def _gen_backward(self, x_ptr, n, k1g, st, prof) -> None:
-        eG = self.eG
-        ops.check(_zero_grad(eG.fp, st), "zero_grad G")
-        ops.check(lib.combat_warp_bwd(x_ptr, self.d_bd.data_ptr(), self.d_bd2.data_ptr(), self.g["grid"].data_ptr(), 0, n, self.hw,
+        eG, s = self.eG, self.cur
+        ops.check(_zero_grad_call(eG.fp, st), "zero_grad G")
+        ops.check(lib.combat_warp_bwd(x_ptr, s.d_bd.data_ptr(), s.d_bd2.data_ptr(), self.g["grid"].data_ptr(), 0, n, self.hw,
                                       self.WARP_GROUPS, self._wpartial.data_ptr(), st), "warp bwd")
         eG.backward_field(self._wpartial, self.WARP_GROUPS, self.hw, float(self.opt.grid_rescale), float(self.opt.L2_weight), st)
         if self.world > 1:
@@ -697,18 +708,12 @@ class InputAwareStep(AlternatedStep):
     passes [aug3(bd) ; aug5(bd2)] share one 2n slot with two loss halves (engine two_loss / half_weights: the n-image
     plans over its halves, so d_bd is AlternatedStep's for the same images); the paired trigger (combat_trigger_pair_fwd / _bwd) makes bd and bd2 in one launch and returns
     the gradient of both noises in one launch.  The blur is the reference's module-level GaussianBlur (:53): kernel 3,
-    sigma in (0.1, 1), whatever --kernel_size / --sigma say (the step keeps a copy of opt with kernel_size 3 and draws
-    from SIGMA_RANGE)."""
+    sigma in (0.1, 1), whatever --kernel_size / --sigma say (FIXED_BLUR)."""
 
-    SIGMA_RANGE = (0.1, 1.0)
-    _PER_N = AlternatedStep._PER_N + ("inputs2", "bd2", "d_cross", "_gen_bwd")
-
-    def __init__(self, netC, netG, clean_model, netF, opt, process_group=None):
-        opt = copy.copy(opt)     # the fixed blur (:53): every blur kernel of the step is built from opt.kernel_size
-        opt.kernel_size = 3
-        super().__init__(netC, netG, clean_model, netF, opt, process_group)
-        self.inputs2 = None
-        self._inputs2_src = None
+    TABLE = (6, 3, 9)   # + the cross images' augmentation table, the blur kernel of sigma_x, the LAB_CROSS rows
+    FIXED_BLUR = True
+    CAN_MERGE_C = False
+    _inputs2_src = None
 
     def run(self, inputs: torch.Tensor, targets_cpu: torch.Tensor, inputs2: torch.Tensor,
             rnd: Optional[InputAwareRandomness] = None, lr_c: Optional[float] = None, lr_g: Optional[float] = None,
@@ -727,52 +732,36 @@ class InputAwareStep(AlternatedStep):
             self._inputs2_src = None
 
     # ---- buffers, table, plans
-    def _setup(self, n: int):
-        if n == self.N:
-            return
-        super()._setup(n)
-        if self.inputs2 is None or self.inputs2.shape[0] != n:
-            dev, hw = self.dev, self.hw
-            self.inputs2 = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)
-            self.bd2 = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)       # inputs_bd2 (:238)
-            self.d_cross = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)   # its gradient
-
-    # [6 aug tables | index_small, index_total | blur kernels of sigma_c, sigma_g, sigma_x (+ 12 bytes of padding) |
-    #  label rows]: rows 0-6 as AlternatedStep, 7 bd_targets, 8 targets (rows 7-8 = the two-half netC pass's labels)
-    @staticmethod
-    def _table_bytes(n: int) -> int:
-        return 6 * n * 16 + 2 * n * 4 + 48 + 9 * n * 8
-
-    @staticmethod
-    def _table_views(raw: torch.Tensor, n: int):
-        o1 = 6 * n * 16
-        o2 = o1 + 2 * n * 4
-        o3 = o2 + 48
-        return (raw[:o1].view(f32).view(6, n, 4), raw[o1:o2].view(torch.int32).view(2, n),
-                raw[o2:o2 + 36].view(f32).view(3, 3), raw[o3:].view(torch.int64).view(9, n))
+    def _build_set(self, n: int):
+        s = super()._build_set(n)
+        dev, hw = self.dev, self.hw
+        s.inputs2 = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)
+        s.bd2 = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)       # inputs_bd2 (:238)
+        s.d_cross = torch.empty(n, 3, hw, hw, dtype=f32, device=dev)   # its gradient
+        return s
 
     def _fill_table_extra(self, hs, rnd, targets_cpu, bd_targets_cpu) -> None:
         hs["k1"][2].copy_(torch.from_numpy(trigger.gaussian_kernel1d(rnd.sigma_x, self.opt.kernel_size)))
-        hs["targets"][7].copy_(bd_targets_cpu)
-        hs["targets"][8].copy_(targets_cpu)
+        hs["targets"][LAB_CROSS][0].copy_(bd_targets_cpu)
+        hs["targets"][LAB_CROSS][1].copy_(targets_cpu)
 
     def _gen_slot(self, n):
         return self.eG.slot("G.pair", 2 * n, self.hw)
 
-    def _gen_plans(self) -> dict:
+    def _gen_plans(self, s) -> dict:
         """The generator over [inputs ; inputs2] runs the n-image plans on the two halves of the 2n slot (views of its
         buffers), forward and backward.  A 2n-image plan picks other tile and statistics partitions, and the UNet's
         bf16 activations and 2 x 2 / 4 x 4 InstanceNorms amplify the different rounding to ~1 % of its output; with the
         n-image plans the first half is AlternatedStep's generator pass bit for bit.  The 2n forward plan is only built
         (it allocates the 2n buffers the halves view), never run."""
-        eG, sG = self.eG, self.sG
-        n, hw = sG.N // 2, self.hw
+        eG, sG = self.eG, s.sG
+        n, hw = s.n, self.hw
         eG.forward_plan(sG)
         sG.buf("g.z", (2 * n, hw, hw, 8))
         share = tuple(k for k, v in sG.bufs.items() if v.dim() and v.shape[0] == sG.N)
         halves = [sG.half_view(k * n, n, share) for k in range(2)]
         fwd = PlanSeq("unet.fwd.halves", [eG.forward_plan(h) for h in halves])
-        self._gen_bwd = [eG.backward_plan(h) for h in halves]
+        s._gen_bwd = [eG.backward_plan(h) for h in halves]
         # a half's output must land in the 2n slot ('<layer>.part': statistics partials of the half's own forward)
         for h in halves:
             bad = [k for k in h.bufs if k in sG.bufs and k not in share and not k.endswith(".part")]
@@ -781,61 +770,60 @@ class InputAwareStep(AlternatedStep):
             self._g_cross = torch.zeros_like(eG.fp.grad)     # the cross half's generator gradient (shared by all batch sizes)
         return dict(G_f=fwd)
 
-    def _c_eval_slots(self, n) -> None:
-        self.sC_eval = self.eC.slot("C.cross2", 2 * n, self.hw)   # [aug3(bd) ; aug5(bd2)]: both halves differentiated
-        self.sC_met = self.eC.slot("C.metric", n, self.hw)
+    def _c_eval_slots(self, s) -> None:
+        s.sC_eval = self.eC.slot("C.cross2", 2 * s.n, self.hw)   # [aug3(bd) ; aug5(bd2)]: both halves differentiated
+        s.sC_met = self.eC.slot("C.metric", s.n, self.hw)
+        s.sC_eval.bufs["targets"], s.sC_met.bufs["targets"] = s.d_targets[LAB_CROSS].view(-1), s.d_targets[LAB_TARGETS]
 
-    def _c_eval_labels(self, lab) -> None:
-        self.sC_train.bufs["targets"], self.sC_eval.bufs["targets"], self.sC_met.bufs["targets"] = \
-            lab[2], lab[7:9].view(-1), lab[0]
+    def _c_eval_fwd_plan(self, s, hb):
+        return self.eC.forward_plan(s.sC_eval, False, 1.0, False, two_loss=True)
 
-    def _c_eval_fwd_plan(self, hb):
-        return self.eC.forward_plan(self.sC_eval, False, 1.0, False, two_loss=True)
-
-    def _c_eval_bwd_plan(self, n, hb):
-        return self.sC_eval, self.eC.backward_eval_plan(self.sC_eval, 1.0, half_weights=(1.0, float(self.opt.cross_weight)))
+    def _c_eval_bwd_plan(self, s, hb):
+        return s.sC_eval, self.eC.backward_eval_plan(s.sC_eval, 1.0, half_weights=(1.0, float(self.opt.cross_weight)))
 
     # ---- the step's pieces
     def _draw(self, targets_cpu, bd_targets_cpu) -> InputAwareRandomness:
         """Reference order (:189-252): num_bd, sigma_c (only if num_bd > 0), aug0, aug1, sigma_g, sigma_x, aug2, aug5
         (cross images, :241), aug3, aug4."""
         n = targets_cpu.shape[0]
-        n_trg = int((targets_cpu == bd_targets_cpu).sum())
-        num_bd = int(np.sum(np.random.rand(n_trg) < self.opt.pc))
-        sigma_c = trigger.sample_sigma(self.SIGMA_RANGE) if num_bd else 0.5
+        num_bd = draw_num_bd(targets_cpu, bd_targets_cpu, self.opt.pc)
+        sigma_c = trigger.sample_sigma(self.sigma_range) if num_bd else 0.5
         aug0, aug1 = self.transforms.sample(n), self.transforms.sample(n)
-        sigma_g = trigger.sample_sigma(self.SIGMA_RANGE)
-        sigma_x = trigger.sample_sigma(self.SIGMA_RANGE)
+        sigma_g = trigger.sample_sigma(self.sigma_range)
+        sigma_x = trigger.sample_sigma(self.sigma_range)
         aug2, aug5, aug3, aug4 = (self.transforms.sample(n) for _ in range(4))
         return InputAwareRandomness(num_bd, sigma_c, sigma_g, [aug0, aug1, aug2, aug3, aug4, aug5], sigma_x=sigma_x)
 
     def _gen_forward(self, x_ptr, n, st, prof) -> None:
         """netG over [inputs ; inputs2].  The second batch's copy sits next to the step's combat_copy3 (it comes from
         its own loader's pinned ring)."""
-        self.inputs2.copy_(self._inputs2_src, non_blocking=True)
-        gin = self.eG.input(self.sG)
+        s = self.cur
+        s.inputs2.copy_(self._inputs2_src, non_blocking=True)
+        gin = self.eG.input(s.sG)
         ops.check(lib.combat_image_to_c8(x_ptr, n, self.hw, gin.data_ptr(), st), "c8 G")
-        ops.check(lib.combat_image_to_c8(self.inputs2.data_ptr(), n, self.hw, gin[n:].data_ptr(), st), "c8 G2")
-        self.pl["G_f"].run(prof)
+        ops.check(lib.combat_image_to_c8(s.inputs2.data_ptr(), n, self.hw, gin[n:].data_ptr(), st), "c8 G2")
+        s.pl["G_f"].run(prof)
 
     def _trigger_g(self, x_ptr, n, k1g, s2) -> None:
         """inputs_bd (blur sigma_g, + squared-error partials) and inputs_bd2 (sigma_x), both on the first batch's
         images (:231-238): one launch."""
-        ops.check(lib.combat_trigger_pair_fwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1g,
-                                              float(self.opt.noise_rate), n, self.hw, self.bd.data_ptr(),
-                                              self.bd2.data_ptr(), self.mse.data_ptr(), s2), "trigger pair")
+        s = self.cur
+        ops.check(lib.combat_trigger_pair_fwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g,
+                                              float(self.opt.noise_rate), n, self.hw, s.bd.data_ptr(),
+                                              s.bd2.data_ptr(), s.mse.data_ptr(), s2), "trigger pair")
 
     def _c_eval_inputs(self, x_ptr, bd_ptr, xC, aug_ptr, n, st) -> None:
         hw = self.hw
         ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[3], n, hw, xC.data_ptr(), None, st), "augment 3")
-        ops.check(lib.combat_augment_fwd(self.bd2.data_ptr(), None, aug_ptr[5], n, hw, xC[n:].data_ptr(), None, st),
+        ops.check(lib.combat_augment_fwd(self.cur.bd2.data_ptr(), None, aug_ptr[5], n, hw, xC[n:].data_ptr(), None, st),
                   "augment 5")
 
     def _c_eval_grads(self, aug_ptr, n, st) -> None:
-        g = self.sC_eval.bufs["g.img"]
-        ops.check(lib.combat_augment_bwd(g.data_ptr(), 8, aug_ptr[3], n, self.hw, self.d_bd.data_ptr(), 0, st),
+        s = self.cur
+        g = s.sC_eval.bufs["g.img"]
+        ops.check(lib.combat_augment_bwd(g.data_ptr(), 8, aug_ptr[3], n, self.hw, s.d_bd.data_ptr(), 0, st),
                   "augment 3 bwd")
-        ops.check(lib.combat_augment_bwd(g[n:].data_ptr(), 8, aug_ptr[5], n, self.hw, self.d_cross.data_ptr(), 0, st),
+        ops.check(lib.combat_augment_bwd(g[n:].data_ptr(), 8, aug_ptr[5], n, self.hw, s.d_cross.data_ptr(), 0, st),
                   "augment 5 bwd")
 
     def _gen_backward(self, x_ptr, n, k1g, st, prof) -> None:
@@ -843,16 +831,16 @@ class InputAwareStep(AlternatedStep):
         the generator backward of each half (:253-254).  A backward plan starts by zeroing the gradient buffer, so the
         cross half runs first and its gradient is set aside; the first half's backward is then AlternatedStep's, and
         the cross gradient is added to it (exactly nothing at cross_weight 0)."""
-        hw = self.hw
+        s, hw = self.cur, self.hw
         l2_scale = float(self.opt.L2_weight) / float(n * 3 * hw * hw)
-        ops.check(lib.combat_trigger_pair_bwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1g,
-                                              float(self.opt.noise_rate), n, hw, self.d_bd.data_ptr(),
-                                              self.d_bd2.data_ptr(), self.bd.data_ptr(), l2_scale, self.d_cross.data_ptr(),
-                                              1, self.sG.buf("g.z", (2 * n, hw, hw, 8)).data_ptr(), st), "trigger pair bwd")
+        ops.check(lib.combat_trigger_pair_bwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g,
+                                              float(self.opt.noise_rate), n, hw, s.d_bd.data_ptr(),
+                                              s.d_bd2.data_ptr(), s.bd.data_ptr(), l2_scale, s.d_cross.data_ptr(),
+                                              1, s.sG.buf("g.z", (2 * n, hw, hw, 8)).data_ptr(), st), "trigger pair bwd")
         grad = self.eG.fp.grad
-        self._gen_bwd[1].run(prof)
+        s._gen_bwd[1].run(prof)
         self._g_cross.copy_(grad)
-        self._gen_bwd[0].run(prof)
+        s._gen_bwd[0].run(prof)
         grad.add_(self._g_cross)
         if self.world > 1 or (FORCE_ALLREDUCE and self.pg is not None):
             torch.distributed.all_reduce(grad, group=self.pg)   # one flat all-reduce
@@ -863,19 +851,19 @@ class InputAwareStep(AlternatedStep):
         (#argmax(pred_cross) == targets, :275)."""
         out = super().read_metrics(reset=False)
         out["loss_cross_sum"], out["cross_correct"] = 0.0, 0
-        for _, sCe, _, _ in self._slot_sets():
-            out["loss_cross_sum"] += float(sCe.bufs["loss1"])
-            out["cross_correct"] += int(sCe.bufs["correct1"][0])
+        for s in self._sets.values():
+            out["loss_cross_sum"] += float(s.sC_eval.bufs["loss1"])
+            out["cross_correct"] += int(s.sC_eval.bufs["correct1"][0])
         if reset:
             self.reset_metrics()
         return out
 
     def reset_metrics(self) -> None:
         super().reset_metrics()
-        for _, sCe, _, _ in self._slot_sets():
+        for s in self._sets.values():
             for k in ("loss1", "correct1"):
-                if k in sCe.bufs:
-                    sCe.bufs[k].zero_()
+                if k in s.sC_eval.bufs:
+                    s.sC_eval.bufs[k].zero_()
 
 
 class ImperceptibleStep(AlternatedStep):
@@ -893,48 +881,38 @@ class ImperceptibleStep(AlternatedStep):
     the module-level T.GaussianBlur(kernel_size=3, sigma=(0.1, 1)) (:52), whatever --kernel_size / --sigma say.  At
     tv_weight 0 the trigger backward is the parent's launch, and the step leaves the parent's bits."""
 
-    SIGMA_RANGE = (0.1, 1.0)
-    _PER_N = AlternatedStep._PER_N + ("tv",)
+    FIXED_BLUR = True    # (the draws keep the parent's order: one sigma per create_inputs_bd call, :172-174 and :203)
+    CAN_MERGE_C = False
 
-    def __init__(self, netC, netG, clean_model, netF, opt, process_group=None):
-        opt = copy.copy(opt)     # the fixed blur (:52): every blur kernel of the step is built from opt.kernel_size
-        opt.kernel_size = 3
-        super().__init__(netC, netG, clean_model, netF, opt, process_group)
-
-    def _setup(self, n: int):
-        if n == self.N:
-            return
-        cached = n in self._sets
-        super()._setup(n)
-        if not cached:
-            self.tv = torch.empty(3 * n, dtype=f32, device=self.dev)   # per (image, channel) total variation of inputs_bd
-
-    def _draw(self, targets_cpu, bd_targets_cpu) -> StepRandomness:
-        """The parent's order (one sigma per create_inputs_bd call, :172-174 and :203), from the fixed range."""
-        return draw_randomness(targets_cpu, bd_targets_cpu, self.opt, self.transforms, self.SIGMA_RANGE)
+    def _build_set(self, n: int):
+        s = super()._build_set(n)
+        s.tv = torch.empty(3 * n, dtype=f32, device=self.dev)   # per (image, channel) total variation of inputs_bd
+        return s
 
     def _trigger_g(self, x_ptr, n, k1g, s2) -> None:
         """inputs_bd of the whole batch (:203) with its squared-error and total-variation partials."""
-        ops.check(lib.combat_trigger_tv_fwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1g,
-                                            float(self.opt.noise_rate), n, self.hw, self.bd.data_ptr(), self.mse.data_ptr(),
-                                            self.tv.data_ptr(), s2), "trigger tv G")
+        s = self.cur
+        ops.check(lib.combat_trigger_tv_fwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g,
+                                            float(self.opt.noise_rate), n, self.hw, s.bd.data_ptr(), s.mse.data_ptr(),
+                                            s.tv.data_ptr(), s2), "trigger tv G")
 
     def _log_terms(self, n, s2, f_logits) -> None:
         """The parent's logged terms + loss_tv (:228, :245) -> acc[2]."""
-        ops.check(lib.combat_log_terms_tv(self.inputs.data_ptr(), self.bd.data_ptr(), self.mse.data_ptr(), self.tv.data_ptr(),
+        s = self.cur
+        ops.check(lib.combat_log_terms_tv(s.inputs.data_ptr(), s.bd.data_ptr(), s.mse.data_ptr(), s.tv.data_ptr(),
                                           n, self.hw, f_logits.data_ptr() if f_logits is not None else None,
                                           self.acc.data_ptr(), self.acc_side.data_ptr(), s2), "log terms tv")
 
     def _gen_backward(self, x_ptr, n, k1g, st, prof) -> None:
         """The parent's, with tv_weight * d loss_tv / d inputs_bd in the image gradient (:234-239)."""
-        hw = self.hw
+        s, hw = self.cur, self.hw
         l2_scale = float(self.opt.L2_weight) / float(n * 3 * hw * hw)
         tv_scale = float(self.opt.tv_weight) / float(n)                        # .mean() over the batch (:228)
-        ops.check(lib.combat_trigger_tv_bwd(x_ptr, self.eG.output(self.sG).data_ptr(), self.P.data_ptr(), k1g,
-                                            float(self.opt.noise_rate), n, hw, self.d_bd.data_ptr(), self.d_bd2.data_ptr(),
-                                            self.bd.data_ptr(), l2_scale, tv_scale, 1,
-                                            self.sG.buf("g.z", (n, hw, hw, 8)).data_ptr(), st), "trigger tv bwd")
-        self._backward_allreduce(self.pl["G_b"], self.eG, prof)
+        ops.check(lib.combat_trigger_tv_bwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g,
+                                            float(self.opt.noise_rate), n, hw, s.d_bd.data_ptr(), s.d_bd2.data_ptr(),
+                                            s.bd.data_ptr(), l2_scale, tv_scale, 1,
+                                            s.sG.buf("g.z", (n, hw, hw, 8)).data_ptr(), st), "trigger tv bwd")
+        self._backward_allreduce(s.pl["G_b"], self.eG, prof)
 
     def read_metrics(self, reset: bool = False) -> Dict[str, float]:
         """AlternatedStep's keys plus loss_tv_sum, the sum of the per-step loss_tv (:245; "TV Loss" = / samples)."""
@@ -945,12 +923,7 @@ class ImperceptibleStep(AlternatedStep):
         return out
 
 
-def _zero_grad(fp, st):
-    from .engine import _zero_grad_call
-    return _zero_grad_call(fp, st)
-
-
-class ClassifierStep:
+class ClassifierStep(PerBatchSize):
     """Phase-C-only training step: the loop bodies of train_clean_classifier.py:75-121 (no generator) and
     train_victim.py:102-141 (frozen generator poisons the images the dataset flags).  Batch order as in
     the victim script: [poisoned images with the trigger, all other images] (:125-127)."""
@@ -972,40 +945,27 @@ class ClassifierStep:
         self.P = trigger.lowpass_matrix(self.hw, opt.ratio).to(self.dev)
         self.k1 = torch.zeros(3, dtype=f32, device=self.dev)
         self.transforms = PostTensorTransform(opt)
-        self.N = 0
-        self._sets: Dict[int, dict] = {}
+        self._sets: Dict[int, SimpleNamespace] = {}
         self._small: Dict[int, tuple] = {}
         self._reducers: Dict = {}
 
-    _PER_N = ("cat_src", "tab_i", "tab_f", "slot", "fwd", "bwd")
-
-    def _setup(self, n):
-        """Buffers, slot and plans are per batch size and cached (as AlternatedStep._setup): the ragged last
-        batch of an epoch gets its own set once, and the loss / accuracy cells of every set survive until
-        `read_metrics` sums (and resets) them all."""
-        if n == self.N:
-            return
-        if self.N:
-            self._sets[self.N] = {k: getattr(self, k) for k in self._PER_N}
-        if n in self._sets:
-            for k, v in self._sets[n].items():
-                setattr(self, k, v)
-            self.N = n
-            return
-        self.N, hw, dev = n, self.hw, self.dev
-        self.cat_src = torch.zeros(2 * n, 3, hw, hw, dtype=f32, device=dev)
-        self.tab_i = torch.zeros(2, n, dtype=torch.int32, device=dev)
-        self.tab_f = torch.zeros(n, 4, dtype=f32, device=dev)
-        self.slot = self.eC.slot("V.train", n, hw)
+    def _build_set(self, n: int) -> SimpleNamespace:
+        hw, dev = self.hw, self.dev
+        s = SimpleNamespace(n=n)
+        s.cat_src = torch.zeros(2 * n, 3, hw, hw, dtype=f32, device=dev)
+        s.tab_i = torch.zeros(2, n, dtype=torch.int32, device=dev)
+        s.tab_f = torch.zeros(n, 4, dtype=f32, device=dev)
+        s.slot = self.eC.slot("V.train", n, hw)
         hb = FUSED_HEAD and type(self.eC) is PreActEngine
-        self.fwd = self.eC.forward_plan(self.slot, True, **(dict(head_bwd=True) if hb else {}))
-        self.bwd = self.eC.backward_train_plan(self.slot, **(dict(head_done=True) if hb else {}))
+        s.fwd = self.eC.forward_plan(s.slot, True, **(dict(head_bwd=True) if hb else {}))
+        s.bwd = self.eC.backward_train_plan(s.slot, **(dict(head_done=True) if hb else {}))
+        return s
 
     def run(self, inputs: torch.Tensor, targets_cpu: torch.Tensor, poisoned_cpu: Optional[torch.Tensor] = None,
             lr: Optional[float] = None) -> None:
         opt = self.opt
         n = inputs.shape[0]
-        self._setup(n)
+        s = self._setup(n)
         hw, st = self.hw, torch.cuda.current_stream().cuda_stream
         targets_cpu = targets_cpu.cpu()
         if poisoned_cpu is None or self.eG is None:
@@ -1013,48 +973,43 @@ class ClassifierStep:
         trg = poisoned_cpu.cpu().nonzero()[:, 0]
         ntrg = (~poisoned_cpu.cpu()).nonzero()[:, 0]      # intent of train_victim.py:121
         nb = int(trg.numel())
-        perm = torch.cat([trg, ntrg]).to(torch.int32)
+        perm, idx_small, idx_total = order_tables(trg, ntrg, nb)
         tot = targets_cpu[perm.long()].clone()
         if nb:
             tot[:nb] = create_targets_bd(targets_cpu[trg], opt)
-        idx = torch.zeros(2, n, dtype=torch.int32)
-        idx[0, :nb] = perm[:nb]
-        idx[1] = perm
-        if nb:
-            idx[1, :nb] = torch.arange(n, n + nb, dtype=torch.int32)
-        self.tab_i.copy_(idx)
+        s.tab_i.copy_(torch.stack([idx_small, idx_total]))
         self.last_poisoned = (trg, nb)     # (image logging: train_victim_wanet.py:127-133)
         aug = self.transforms.sample(n)
         if aug is not None:
-            self.tab_f.copy_(torch.from_numpy(aug))
-        self.cat_src[:n].copy_(inputs)
-        h = self.eC.head_bufs(self.slot)
+            s.tab_f.copy_(torch.from_numpy(aug))
+        s.cat_src[:n].copy_(inputs)
+        h = self.eC.head_bufs(s.slot)
         h["targets"].copy_(tot)
         self.eC.refresh()
         if nb and self.wanet:
             g = self.eG.forward_grid(hw, float(opt.grid_rescale), st)
-            ops.check(lib.combat_warp_fwd(self.cat_src.data_ptr(), self.tab_i[0].data_ptr(), g["grid"].data_ptr(), 0, nb, hw,
-                                          self.cat_src[n:].data_ptr(), st), "warp")
+            ops.check(lib.combat_warp_fwd(s.cat_src.data_ptr(), s.tab_i[0].data_ptr(), g["grid"].data_ptr(), 0, nb, hw,
+                                          s.cat_src[n:].data_ptr(), st), "warp")
         elif nb:
             self.eG.refresh()
             nbk = min(bucket(nb), n)
             if nbk not in self._small:
-                s = self.eG.slot("V.small", nbk, hw)
-                self._small[nbk] = (s, self.eG.forward_plan(s), torch.zeros(nbk, 3, hw, hw, dtype=f32, device=self.dev))
+                small = self.eG.slot("V.small", nbk, hw)
+                self._small[nbk] = (small, self.eG.forward_plan(small), torch.zeros(nbk, 3, hw, hw, dtype=f32, device=self.dev))
             sS, plan_small, tochange = self._small[nbk]
             self.k1.copy_(torch.from_numpy(trigger.gaussian_kernel1d(
                 trigger.sample_sigma(getattr(opt, "sigma", (0.1, 1.0))), opt.kernel_size)))
-            ops.check(lib.combat_augment_fwd(self.cat_src.data_ptr(), self.tab_i[0].data_ptr(), None, nbk, hw,
+            ops.check(lib.combat_augment_fwd(s.cat_src.data_ptr(), s.tab_i[0].data_ptr(), None, nbk, hw,
                                              self.eG.input(sS).data_ptr(), tochange.data_ptr(), st), "gather poisoned")
             plan_small.run()
             ops.check(lib.combat_trigger_fwd(tochange.data_ptr(), self.eG.output(sS).data_ptr(), self.P.data_ptr(),
                                              self.k1.data_ptr(), float(opt.noise_rate), nb, hw, None,
-                                             self.cat_src[n:].data_ptr(), None, None, st), "trigger")
-        ops.check(lib.combat_augment_fwd(self.cat_src.data_ptr(), self.tab_i[1].data_ptr(),
-                                         self.tab_f.data_ptr() if aug is not None else None, n, hw,
-                                         self.eC.input(self.slot).data_ptr(), None, st), "augment")
-        self.fwd.run()
-        backward_allreduce(self.bwd, self.eC, self.pg, self.world, self._reducers)   # buckets overlap the backward
+                                             s.cat_src[n:].data_ptr(), None, None, st), "trigger")
+        ops.check(lib.combat_augment_fwd(s.cat_src.data_ptr(), s.tab_i[1].data_ptr(),
+                                         s.tab_f.data_ptr() if aug is not None else None, n, hw,
+                                         self.eC.input(s.slot).data_ptr(), None, st), "augment")
+        s.fwd.run()
+        backward_allreduce(s.bwd, self.eC, self.pg, self.world, self._reducers)   # buckets overlap the backward
         self.eC.fp.sgd_step(float(lr if lr is not None else opt.lr_C), grad_scale=1.0 / self.world)
         self.eC.mark_weights_dirty()
 
@@ -1064,18 +1019,14 @@ class ClassifierStep:
         trg, nb = getattr(self, "last_poisoned", (None, 0))
         if not nb:
             return None
-        n = self.N
-        return self.cat_src[:n][trg.to(self.dev)].clone(), self.cat_src[n:n + nb].clone()
-
-    def _slots(self):
-        out = [self.slot] if self.N else []
-        return out + [d["slot"] for n, d in self._sets.items() if n != self.N]
+        s = self.cur
+        return s.cat_src[:s.n][trg.to(self.dev)].clone(), s.cat_src[s.n:s.n + nb].clone()
 
     def read_metrics(self, reset=False):
         """Running loss sum / correct count over every batch size run since the last reset (one host sync)."""
         out = {"loss_sum": 0.0, "correct": 0}
-        for slot in self._slots():
-            h = self.eC.head_bufs(slot)
+        for s in self._sets.values():
+            h = self.eC.head_bufs(s.slot)
             out["loss_sum"] += float(h["loss"])
             out["correct"] += int(h["correct"][0])
             if reset:

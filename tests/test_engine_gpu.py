@@ -18,6 +18,7 @@ Two references, two tolerances (both stated at each check):
     checks therefore bound forward error at 5e-2 and gradient error at 0.5, and assert that the
     engine is no further from fp32 than the emulation is (x1.6).
 """
+import copy
 import os
 import sys
 
@@ -1082,6 +1083,96 @@ def test_classifier_step_metrics_cover_ragged_batches(mods):
     assert totals[0]["correct"] == totals[1]["correct"] and 0 <= totals[0]["correct"] <= n_all
     # the reference accumulates the batch-MEAN loss (train_victim.py:139): ~ln(10) per batch, over ALL four batches
     assert 1.5 * len(batches) < totals[0]["loss_sum"] < 4.0 * len(batches)
+
+
+def _family_case(mods, family):
+    """(initial networks on the CPU, constructor of the step from copies of them, run(st, i, x, t, x2)) of one step family."""
+    step_mod, nets = mods["step"], mods["nets"]
+    netc, clean, netg, netf = _build(mods, [0, 1, 2, 3])
+    draws = [(3, 0.4, 0.7, 0.5), (0, 0.5, 0.6, 0.9), (2, 0.8, 0.3, 0.6)]       # num_bd, sigma_c, sigma_g, sigma_x per step
+    opt = Opt()
+    if family == "wanet":
+        opt.s, opt.grid_rescale = 2, 0.15
+        netg = seeded(lambda: nets.GridGenerator(opt), 2)
+    opt.cross_weight, opt.tv_weight = 0.2, 0.05
+    if family == "classifier":
+        def make(c, g, k, f):
+            return step_mod.ClassifierStep(c, opt, g.eval())
+
+        def run(st, i, x, t, x2):
+            torch.manual_seed(50 + i)          # ClassifierStep takes no draws: it samples the blur sigma itself
+            poisoned = torch.zeros(t.shape[0], dtype=torch.bool)
+            poisoned[:draws[i][0]] = True
+            st.run(x, t, poisoned)
+        return (netc, clean, netg, netf), make, run
+    cls = {"alternated": step_mod.AlternatedStep, "inputaware": step_mod.InputAwareStep,
+           "imperceptible": step_mod.ImperceptibleStep, "wanet": step_mod.WanetStep}[family]
+
+    def make(c, g, k, f):
+        return cls(c, g, k.eval(), f.eval(), opt)
+
+    def run(st, i, x, t, x2):
+        nb, sc, sg, sx = draws[i]
+        if family == "inputaware":
+            st.run(x, t, x2, step_mod.InputAwareRandomness(nb, sc, sg, [None] * 6, sigma_x=sx))
+        else:
+            st.run(x, t, step_mod.StepRandomness(nb, sc, sg, [None] * 5))
+    return (netc, clean, netg, netf), make, run
+
+
+@pytest.mark.parametrize("family", ["alternated", "inputaware", "imperceptible", "wanet", "classifier"])
+def test_metrics_and_weights_survive_batch_size_switches(mods, family):
+    """Batches of 16, 12 and 16 images (the third returns to the first size's buffers, slots and plans) in deterministic
+    mode with explicit draws, twice from copies of the same networks: run A reads and resets the metrics after every
+    step, run B reads them once at the end.  Switching between the per-batch-size sets must neither touch the
+    arithmetic -- (a) netC's and netG's final parameters are bit-identical -- nor lose or double a metric cell: (b) B saw
+    44 samples, (c) each integer counter of B is the sum of A's three readings, (d) each float sum of B is the host sum
+    of A's within relative 1e-6 (B's cells add the steps on the device in fp32: one rounding, 6e-8), and (e) after A's
+    last reset everything reads zero.  ("samples" is reported as the divisor max(samples, 1): the step's own count is
+    checked for (e); ClassifierStep reports no sample count.)"""
+    engine = mods["engine"]
+    nets0, make, run = _family_case(mods, family)
+    gen = torch.Generator().manual_seed(21)
+    batches = []
+    for b in (16, 12, 16):
+        x, x2 = ((torch.randint(0, 256, (b, 3, 32, 32), generator=gen).float() / 255 - 0.5) / 0.5 for _ in range(2))
+        t = torch.randint(0, 10, (b,), generator=gen)
+        t[:5] = 0
+        batches.append((x.cuda(), t, x2.cuda()))
+    prev = engine.deterministic()
+    engine.set_deterministic(True)
+    out = []
+    try:
+        for every_step in (True, False):
+            netc, clean, netg, netf = (copy.deepcopy(m).cuda() for m in nets0)
+            st = make(netc, netg, clean, netf)
+            reads = []
+            for i, (x, t, x2) in enumerate(batches):
+                run(st, i, x, t, x2)
+                if every_step:
+                    reads.append(st.read_metrics(reset=True))
+            reads.append(st.read_metrics())
+            torch.cuda.synchronize()
+            out.append((reads, [p.detach().clone() for m in (netc, netg) for p in m.parameters()], getattr(st, "samples", None)))
+    finally:
+        engine.set_deterministic(prev)
+    (reads_a, params_a, samples_a), (reads_b, params_b, samples_b) = out
+    assert len(params_a) == len(params_b) > 0 and all(torch.equal(u, v) for u, v in zip(params_a, params_b))     # (a)
+    (*steps_a, after_a), (m_b,) = reads_a, reads_b
+    print(family, "A:", steps_a, "B:", m_b)
+    if "samples" in m_b:
+        assert m_b["samples"] == 44 and [m["samples"] for m in steps_a] == [16, 12, 16]                         # (b)
+        assert (samples_a, samples_b) == (0, 44)
+    keys = [k for k in m_b if k != "samples"]
+    assert any(isinstance(m_b[k], int) for k in keys) and any(isinstance(m_b[k], float) for k in keys)
+    for k in keys:
+        total = sum(m[k] for m in steps_a)
+        if isinstance(m_b[k], int):
+            assert m_b[k] == total, (k, m_b[k], total)                                                           # (c)
+        else:
+            assert abs(m_b[k] - total) <= 1e-6 * abs(total), (k, m_b[k], total)                                  # (d)
+        assert after_a[k] == 0, (k, after_a[k])                                                                  # (e)
+    assert any(m_b[k] != 0 for k in keys if isinstance(m_b[k], float))
 
 
 # ---------------------------------------------------------------- evaluation loops and the victim / clean-classifier step

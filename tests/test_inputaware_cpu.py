@@ -74,10 +74,9 @@ def test_draw_ignores_the_blur_flags():
 
 
 def test_step_table_layout():
-    from combat_amd.step import InputAwareStep
+    from combat_amd.step import InputAwareStep, step_table
     for n in (1, 7, 16, 128):
-        raw = torch.zeros(InputAwareStep._table_bytes(n), dtype=torch.uint8)
-        aug, idx, k1, lab = InputAwareStep._table_views(raw, n)
+        raw, aug, idx, k1, lab = step_table(n, *InputAwareStep.TABLE)
         assert aug.shape == (6, n, 4) and idx.shape == (2, n) and k1.shape == (3, 3) and lab.shape == (9, n)
         spans = sorted((t.data_ptr() - raw.data_ptr(), t.data_ptr() - raw.data_ptr() + t.numel() * t.element_size())
                        for t in (aug, idx, k1, lab))
