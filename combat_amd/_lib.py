@@ -127,6 +127,8 @@ SIGNATURES = {
     "combat_head_bwd_weights": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "combat_prune_sweep": (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "combat_feature_colsum": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "combat_strip_superimpose": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "combat_strip_entropy": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "combat_comm_unique_id": (C.c_int, [c_vp]),
     "combat_comm_init_rank": (C.c_int, [C.POINTER(c_vp), c_i32, c_vp, c_i32]),
     "combat_comm_destroy": (C.c_int, [c_vp]),

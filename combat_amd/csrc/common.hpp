@@ -100,6 +100,18 @@ __device__ __forceinline__ void load8f(const float *p, float (&v)[8]) {
 
 __device__ __forceinline__ float round_bf16(float f) { return bf16_bits_to_f32(f32_to_bf16_bits(f)); }
 
+// One pixel of an NHWC c8 hi/lo image (include/combat_hip.h, "images entering a network"): channels 0-2 = bf16(x),
+// 3-5 = bf16(x - bf16(x)), 6-7 = 0.  Shared by every kernel that writes a network's input buffer.
+__device__ __forceinline__ uint4 hilo_pixel(float r, float g, float b) {
+    const float hr = round_bf16(r), hg = round_bf16(g), hb = round_bf16(b);
+    uint4 u;
+    u.x = pack_bf16x2(hr, hg);
+    u.y = pack_bf16x2(hb, r - hr);
+    u.z = pack_bf16x2(g - hg, b - hb);
+    u.w = 0;
+    return u;
+}
+
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // combat_set_deterministic / COMBAT_DETERMINISTIC=1 (capi.cpp): launches pick their order-independent forms

@@ -99,16 +99,6 @@ __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const combat_pa
 }
 
 // ------------------------------------------------------------------ image layout
-__device__ __forceinline__ uint4 hilo_pixel(float r, float g, float b) {
-    const float hr = round_bf16(r), hg = round_bf16(g), hb = round_bf16(b);
-    uint4 u;
-    u.x = pack_bf16x2(hr, hg);
-    u.y = pack_bf16x2(hb, r - hr);
-    u.z = pack_bf16x2(g - hg, b - hb);
-    u.w = 0;
-    return u;
-}
-
 __global__ __launch_bounds__(256) void image_to_c8_kernel(const float *__restrict__ x, int n, int hw2,
                                                           uint4 *__restrict__ out) {
     const long total = (long)n * hw2;

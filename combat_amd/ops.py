@@ -363,6 +363,25 @@ def feature_colsum(pooled, acc) -> None:
           "n=%d in=%d" % (n, fin))
 
 
+def strip_superimpose(backgrounds, dataset, index, norm_cols, out_c8) -> None:
+    """out_c8 image b * S + s = backgrounds[b] + dataset[index[b][s]] saturated, / 255, columns < norm_cols normalised:
+    uint8 [B][hw][hw][3], uint8 [n_data][hw][hw][3], int32 [B][S] (include/combat_hip.h, combat_strip_superimpose)."""
+    b, hw = backgrounds.shape[0], backgrounds.shape[1]
+    s = index.shape[1]
+    if out_c8.shape[0] < b * s or tuple(out_c8.shape[1:]) != (hw, hw, 8) or tuple(dataset.shape[1:]) != (hw, hw, 3):
+        raise ValueError("strip_superimpose: out_c8 %s / dataset %s do not hold %d x %d blends of %d x %d pixels"
+                         % (tuple(out_c8.shape), tuple(dataset.shape), b, s, hw, hw))
+    check(lib.combat_strip_superimpose(backgrounds.data_ptr(), b, dataset.data_ptr(), dataset.shape[0], index.data_ptr(),
+                                       s, hw, norm_cols, out_c8.data_ptr(), _stream()),
+          "combat_strip_superimpose", "B=%d S=%d hw=%d norm_cols=%d" % (b, s, hw, norm_cols))
+
+
+def strip_entropy(logits, b, s, out) -> None:
+    """out[i] (fp32 [b]) = the mean entropy of rows [i * s, (i + 1) * s) of logits (fp32 [>= b * s][classes])."""
+    check(lib.combat_strip_entropy(logits.data_ptr(), b, s, logits.shape[1], out.data_ptr(), _stream()),
+          "combat_strip_entropy", "B=%d S=%d classes=%d" % (b, s, logits.shape[1]))
+
+
 def sgd_nesterov(ptrs, sizes, count, max_size, lr, momentum, weight_decay, grad_scale, first_step) -> None:
     check(lib.combat_sgd_nesterov(ptrs.data_ptr(), sizes.data_ptr(), count, max_size, lr, momentum, weight_decay,
                                   grad_scale, int(first_step), _stream()), "combat_sgd_nesterov", "count=%d" % count)

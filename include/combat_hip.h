@@ -508,6 +508,35 @@ int combat_prune_sweep(const float *pooled, int32_t n, const float *W, const flo
 int combat_feature_colsum(const float *pooled, int32_t n, int32_t in, double *acc, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * STRIP defense (defenses/STRIP/STRIP.py).  For a background image the reference draws n_sample test images, builds each
+ * blend on the host (:60-64 cv2.addWeighted(background, 1, overlay, 1, 0), then ToTensor and Normalize, :87-96), stacks
+ * and uploads them (:75), and scores the background by the mean entropy of the classifier's sigmoid outputs (:76-78).
+ *
+ * combat_strip_superimpose: backgrounds uint8 [B][hw][hw][3], dataset uint8 [n_data][hw][hw][3] (device resident for the
+ * whole run), index int32 [B][S], out_c8 = the classifier's input buffer, [>= B * S][hw][hw][8] bf16 hi/lo pixels (the
+ * layout combat_image_to_c8 writes).  Image b * S + s, pixel (y, x), channel c:
+ *   v = float(min(backgrounds[b][y][x][c] + dataset[index[b][s]][y][x][c], 255)) / 255.0f      (a true division: ToTensor)
+ *   if (x < norm_cols) v = (v - 0.5f) / 0.5f
+ * then the hi/lo split of combat_image_to_c8.  norm_cols = 3 is the reference: its Normalize.__call__ (:27-31) runs on
+ * the CHW tensor and indexes x[:, :, channel], the WIDTH axis, so only columns 0..2 are normalised and columns 3.. stay in
+ * [0, 1]; norm_cols = hw normalises the whole image.  Replaces _superimpose, ToTensor, Normalize and
+ * torch.stack(...).to(device), :60-75: no float image exists.  An index outside [0, n_data) adds NOTHING (the blend is
+ * the background itself); nothing outside the dataset is read.  COMBAT_EINVAL for a NULL pointer, hw not in
+ * {32, 64, 224}, norm_cols outside 0..hw, B * S > INT32_MAX, a negative count, or sources not 4-byte / out_c8 not 16-byte
+ * aligned; B == 0 or S == 0 is a no-op.
+ *
+ * combat_strip_entropy: logits fp32 [B * S][classes] -> out fp32 [B],
+ *   out[b] = -(sum over the S rows of b and all classes of p * log2f(p)) / S,   p = 1.0f / (1.0f + expf(-logit)),
+ * terms in fp32 (precise expf / log2f) as the reference computes them, their sum in fp64 in a fixed order (bit-identical
+ * from run to run).  A term that is NaN -- p == 0 (0 * -inf) or a NaN logit -- adds nothing: np.nansum, :77.  Replaces
+ * torch.sigmoid(...).cpu().numpy() and the numpy entropy of :76-78.  COMBAT_EINVAL for classes outside 1..16, S < 1,
+ * B < 0, B * S > INT32_MAX, a NULL pointer; B == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------ */
+int combat_strip_superimpose(const void *backgrounds, int32_t B, const void *dataset, int32_t n_data, const int32_t *index,
+                             int32_t S, int32_t hw, int32_t norm_cols, void *out_c8, void *stream);
+int combat_strip_entropy(const float *logits, int32_t B, int32_t S, int32_t classes, float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * SGD(momentum, weight_decay, nesterov) over a list of tensors (train_generator.py:123,125,212,255;
  * torch.optim.SGD semantics: g += wd*p; buf = first ? g : mu*buf + g; p -= lr*(g + mu*buf)).
  * ptrs: DEVICE array of 3*count pointers (param, grad, buf triples); sizes: DEVICE int64[count].
