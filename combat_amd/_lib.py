@@ -129,6 +129,11 @@ SIGNATURES = {
     "combat_feature_colsum": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "combat_strip_superimpose": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "combat_strip_entropy": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "combat_nc_blend": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp,
+                                  c_vp]),
+    "combat_nc_update": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32,
+                                   c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_i32,
+                                   c_vp, c_vp]),
     "combat_comm_unique_id": (C.c_int, [c_vp]),
     "combat_comm_init_rank": (C.c_int, [C.POINTER(c_vp), c_i32, c_vp, c_i32]),
     "combat_comm_destroy": (C.c_int, [c_vp]),

@@ -10,7 +10,13 @@ so here the curve costs one clean pass, one backdoor pass and combat_prune_sweep
 STRIP (reference defenses/STRIP/STRIP.py; Gao et al., ACSAC 2019): a background image is superimposed with n_sample test
 images and scored by the mean entropy of the classifier's predictions on the blends.  The reference builds every blend on
 the host (:60-75); here combat_strip_superimpose writes the classifier's input buffer from the uint8 sources and
-combat_strip_entropy reads the head's logits, a group of backgrounds per classifier pass."""
+combat_strip_entropy reads the head's logits, a group of backgrounds per classifier pass.
+
+Neural Cleanse (reference defenses/neural_cleanse/detecting.py, neural_cleanse.py; Wang et al., IEEE S&P 2019): per target
+label a mask and a pattern are optimised with Adam so that every blended test image is classified as the label; the L1
+norms of the masks are compared by their median absolute deviation.  A whole optimisation step -- combat_nc_blend, the
+classifier's eval forward and input gradient, combat_nc_update -- is one replayed plan over device cells (DESIGN.md
+section 10); the recorder, the outlier test and the result file are host code."""
 from __future__ import annotations
 
 import os
@@ -274,3 +280,401 @@ class Strip:
             eng.forward_plan(slot, False).run()
             ops.strip_entropy(eng.head_bufs(slot)["logits"], g, S, out[g0:g0 + g])
         return out
+
+
+# ---------------------------------------------------------------------------------------------- Neural Cleanse
+
+# The pattern's Normalize (detecting.py:29-31, :76-78): CIFAR's statistics, although the test images are in [-1, 1] -- and
+# Normalize.__call__ (networks/models.py:22-26) indexes x[:, channel] of the [3][hw][hw] pattern, which has no batch axis:
+# the ROW axis.  Rows 0..2 of every colour plane become (raw - mean[row]) / std[row]; rows 3.. stay raw.  The reference's
+# arithmetic, kept because published numbers come from it.
+NC_MEAN = (0.4914, 0.4822, 0.4465)
+NC_STD = (0.247, 0.243, 0.261)
+
+
+def _nc_row_norm(hw: int, mean, std, dtype) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(shift, scale) [1][hw][1] of the pattern's normalisation: p = (raw - shift) / scale, row by row."""
+    shift, scale = torch.zeros(1, hw, 1, dtype=dtype), torch.ones(1, hw, 1, dtype=dtype)
+    for row in range(3):
+        shift[0, row, 0], scale[0, row, 0] = mean[row], std[row]
+    return shift, scale
+
+
+def _nc_raw(t: torch.Tensor, epsilon: float) -> torch.Tensor:
+    """get_raw_mask / get_raw_pattern (detecting.py:35-41) in the dtype of `t`."""
+    return torch.tanh(t) / (2 + epsilon) + 0.5
+
+
+def _nc_pixels(images_u8, dtype) -> torch.Tensor:
+    """[n][3][hw][hw] `dtype` of uint8 [n][hw][hw][3]: ToTensor's true division by 255, then Normalize(0.5, 0.5)."""
+    x = torch.as_tensor(np.asarray(images_u8)).permute(0, 3, 1, 2).to(dtype)
+    return (x / 255 - 0.5) / 0.5
+
+
+def nc_blend_reference(images_u8, mask_tanh, pattern_tanh, epsilon: float = 1e-7, mean=NC_MEAN, std=NC_STD) -> np.ndarray:
+    """combat_nc_blend's arithmetic restated on the host in fp32: float32 [n][3][hw][hw] of uint8 [n][hw][hw][3] images,
+    (1 - m) * x + m * p (detecting.py:27-33)."""
+    f32 = torch.float32
+    m = _nc_raw(torch.as_tensor(np.asarray(mask_tanh), dtype=f32).reshape(1, 1, *np.shape(mask_tanh)[-2:]), epsilon)
+    raw = _nc_raw(torch.as_tensor(np.asarray(pattern_tanh), dtype=f32), epsilon)
+    shift, scale = _nc_row_norm(raw.shape[-2], mean, std, f32)
+    p = (raw - shift) / scale
+    x = _nc_pixels(images_u8, f32)
+    return ((1 - m) * x + m * p[None]).numpy()
+
+
+def nc_gradients_reference(g_img, images_u8, mask_tanh, pattern_tanh, cost: float, epsilon: float = 1e-7, mean=NC_MEAN,
+                           std=NC_STD) -> Tuple[np.ndarray, np.ndarray]:
+    """combat_nc_update's gradients in fp64, taking the classifier's input gradient g_img [n][3][hw][hw] as given:
+    (d mask_tanh [hw][hw], d pattern_tanh [3][hw][hw]) of  sum(g * blend) + cost * |raw mask|_1."""
+    f64 = torch.float64
+    g = torch.as_tensor(np.asarray(g_img), dtype=f64)
+    mt = torch.as_tensor(np.asarray(mask_tanh), dtype=f64).reshape(*np.shape(mask_tanh)[-2:])
+    pt = torch.as_tensor(np.asarray(pattern_tanh), dtype=f64)
+    shift, sd = _nc_row_norm(pt.shape[-2], mean, std, f64)
+    m = _nc_raw(mt, epsilon)
+    p = (_nc_raw(pt, epsilon) - shift) / sd
+    x = _nc_pixels(images_u8, f64)
+    gm = (g * (p[None] - x)).sum(dim=(0, 1))
+    gp = g.sum(dim=0) * m[None] / sd
+    d_mask = (gm + float(cost)) * (1 - torch.tanh(mt) ** 2) / (2 + epsilon)
+    d_pattern = gp * (1 - torch.tanh(pt) ** 2) / (2 + epsilon)
+    return d_mask.numpy(), d_pattern.numpy()
+
+
+def nc_adam_reference(param, grad, exp_avg, exp_avg_sq, t: int, lr: float, beta1: float = 0.5, beta2: float = 0.9,
+                      eps: float = 1e-8) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """One torch.optim.Adam step (no weight decay, no amsgrad) as combat_nc_update takes it, `t` steps having been taken
+    before: fp32 moments and update, the bias corrections in fp64 from the fp32 betas.  Returns (param, exp_avg,
+    exp_avg_sq) as new float32 arrays."""
+    one = np.float32(1)
+    b1, b2, lr32, eps32 = np.float32(beta1), np.float32(beta2), np.float32(lr), np.float32(eps)
+    g = np.asarray(grad, dtype=np.float32)
+    m1 = b1 * np.asarray(exp_avg, dtype=np.float32) + (one - b1) * g
+    m2 = b2 * np.asarray(exp_avg_sq, dtype=np.float32) + (one - b2) * g * g
+    bc1, bc2 = 1.0 - float(b1) ** (t + 1), 1.0 - float(b2) ** (t + 1)
+    step_size, bc2_sqrt = np.float32(float(lr32) / bc1), np.float32(np.sqrt(bc2))
+    new = np.asarray(param, dtype=np.float32) - step_size * (m1 / (np.sqrt(m2) / bc2_sqrt + eps32))
+    return new.astype(np.float32), m1.astype(np.float32), m2.astype(np.float32)
+
+
+def nc_anomaly_index(l1_norms) -> Tuple[np.float32, np.float32, np.float32]:
+    """(median, MAD, anomaly index) of neural_cleanse.py:16-19 in fp32: torch.median is the LOWER middle value of an even
+    count, MAD = 1.4826 * median(|l - median|), index = |min(l) - median| / MAD."""
+    v = np.asarray(l1_norms, dtype=np.float32).reshape(-1)
+    if v.size == 0:
+        raise ValueError("nc_anomaly_index: no L1 norms")
+
+    def lower_median(a):
+        return np.sort(a)[(a.size - 1) // 2]
+
+    median = lower_median(v)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mad = np.float32(1.4826) * lower_median(np.abs(v - median))
+        return median, mad, np.abs(v.min() - median) / mad
+
+
+def nc_flagged_labels(l1_norms, idx_mapping=None):
+    """[(label, norm)] by ascending norm (neural_cleanse.py:39-47): labels whose norm is not above the median and lies
+    more than 2 MAD from it.  idx_mapping {label: position in l1_norms}; default: the labels are the positions."""
+    v = np.asarray(l1_norms, dtype=np.float32).reshape(-1)
+    median, mad, _ = nc_anomaly_index(v)
+    if idx_mapping is None:
+        idx_mapping = {i: i for i in range(v.size)}
+    flagged = []
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for label, at in idx_mapping.items():
+            if v[at] > median:
+                continue
+            if np.abs(v[at] - median) / mad > 2:
+                flagged.append((label, v[at]))
+    return sorted(flagged, key=lambda item: item[1])
+
+
+def nc_verdict(l1_norms, idx_mapping=None) -> Tuple[bool, str]:
+    """(backdoored?, the console lines of neural_cleanse.py:14-27 and :49-51)."""
+    v = np.asarray(l1_norms, dtype=np.float32).reshape(-1)
+    median, mad, index = nc_anomaly_index(v)
+    backdoored = not index < 2
+    text = "-" * 30 + "\nDetermining whether model is backdoor\n"
+    text += "Median: {}, MAD: {}\nAnomaly index: {}\n".format(float(median), float(mad), float(index))
+    text += "This is a backdoor model\n" if backdoored else "Not a backdoor model\n"
+    text += "Flagged label list: {}\n".format(
+        ",".join("{}: {}".format(label, float(norm)) for label, norm in nc_flagged_labels(v, idx_mapping)))
+    return backdoored, text
+
+
+def write_nc_result(path: str, l1_norms) -> None:
+    """Appends the two lines of neural_cleanse.py:32-37: "median, MAD, anomaly index", then the norms, comma separated;
+    fp32 values as numpy prints them."""
+    v = np.asarray(l1_norms, dtype=np.float32).reshape(-1)
+    median, mad, index = nc_anomaly_index(v)
+    with open(path, "a+") as f:
+        f.write(str(median) + ", " + str(mad) + ", " + str(index) + "\n")
+        f.write(", ".join(str(value) for value in v) + "\n")
+
+
+class NeuralCleanseRecorder:
+    """The reference's Recorder (detecting.py:88-120) and the epoch tail of train_step (:208-284) as host code:
+    end_epoch() takes an epoch's averages, keeps the best mask and pattern, moves the cost and says whether to stop.
+    `cost` is what the next epoch's L1 term is weighted with."""
+
+    def __init__(self, opt, verbose: bool = True):
+        self.opt, self.verbose = opt, verbose
+        self.mask_best = self.pattern_best = None
+        self.reg_best = float("inf")
+        self.cost_set_counter = self.cost_up_counter = self.cost_down_counter = 0
+        self.cost_up_flag = self.cost_down_flag = False
+        self.early_stop_counter = 0
+        self.early_stop_reg_best = self.reg_best
+        self.cost = opt.init_cost
+        self.cost_multiplier_up = opt.cost_multiplier
+        self.cost_multiplier_down = opt.cost_multiplier ** 1.5
+        self.epochs = 0
+        self.stopped = False
+
+    def _say(self, text: str) -> None:
+        if self.verbose:
+            print(text)
+
+    def reset_state(self) -> None:
+        self.cost = self.opt.init_cost
+        self.cost_up_counter = self.cost_down_counter = 0
+        self.cost_up_flag = self.cost_down_flag = False
+        self._say("Initialize cost to {:f}".format(self.cost))
+
+    def end_epoch(self, avg_loss_ce, avg_loss_reg, avg_loss_acc, snapshot, on_best=None) -> bool:
+        """avg_*: the means of the epoch's per-batch values (fp32, as torch.mean of the reference's lists); snapshot() ->
+        (raw mask [1][hw][hw], raw pattern [3][hw][hw]) of the parameters as they are now, called only when a copy is
+        kept; on_best(recorder) after a new best (the reference saves its images there).  True: early stop."""
+        opt = self.opt
+        avg_loss_reg, avg_loss_acc = np.float32(avg_loss_reg), np.float32(avg_loss_acc)
+        self.epochs += 1
+        if avg_loss_acc >= opt.atk_succ_threshold and avg_loss_reg < self.reg_best:
+            self.mask_best, self.pattern_best = snapshot()
+            self.reg_best = avg_loss_reg
+            if on_best is not None:
+                on_best(self)
+            self._say(" Updated !!!")
+        stop = False
+        if opt.early_stop:
+            if self.reg_best < float("inf"):
+                if self.reg_best >= np.float32(opt.early_stop_threshold) * np.float32(self.early_stop_reg_best):
+                    self.early_stop_counter += 1
+                else:
+                    self.early_stop_counter = 0
+            self.early_stop_reg_best = min(self.early_stop_reg_best, self.reg_best)
+            if self.cost_down_flag and self.cost_up_flag and self.early_stop_counter >= opt.early_stop_patience:
+                self._say("Early_stop !!!")
+                stop = True
+        if not stop:
+            if self.cost == 0 and avg_loss_acc >= opt.atk_succ_threshold:
+                self.cost_set_counter += 1
+                if self.cost_set_counter >= opt.patience:
+                    self.reset_state()
+            else:
+                self.cost_set_counter = 0
+            if avg_loss_acc >= opt.atk_succ_threshold:
+                self.cost_up_counter += 1
+                self.cost_down_counter = 0
+            else:
+                self.cost_up_counter = 0
+                self.cost_down_counter += 1
+            if self.cost_up_counter >= opt.patience:
+                self.cost_up_counter = 0
+                self._say("Up cost from {} to {}".format(self.cost, self.cost * self.cost_multiplier_up))
+                self.cost *= self.cost_multiplier_up
+                self.cost_up_flag = True
+            elif self.cost_down_counter >= opt.patience:
+                self.cost_down_counter = 0
+                self._say("Down cost from {} to {}".format(self.cost, self.cost / self.cost_multiplier_down))
+                self.cost /= self.cost_multiplier_down
+                self.cost_down_flag = True
+            if self.mask_best is None:                           # "Save the final version"
+                self.mask_best, self.pattern_best = snapshot()
+        self.stopped = stop
+        return stop
+
+
+def nc_epoch_averages(stats: np.ndarray) -> Tuple[np.float32, np.float32, np.float32, float]:
+    """(mean loss_ce, mean loss_reg, mean per-batch accuracy in percent, accuracy over all images in percent) of an epoch's
+    statistics rows [steps][4] = (loss_ce, correct, loss_reg, n), detecting.py:199-216 and :229."""
+    s = np.asarray(stats, dtype=np.float32)
+    acc = s[:, 1] * np.float32(100.0) / s[:, 3]
+    return (np.mean(s[:, 0], dtype=np.float32), np.mean(s[:, 2], dtype=np.float32), np.mean(acc, dtype=np.float32),
+            float(s[:, 1].sum(dtype=np.float64) * 100.0 / s[:, 3].sum(dtype=np.float64)))
+
+
+class NeuralCleanse:
+    """optimise() the mask and pattern of one target label against the classifier `netC` (a combat_amd.nets
+    PreActResNet18 in eval mode) over `dataset_u8`, the test set as uint8 [n][3][hw][hw] (combat_amd.data's layout) or
+    [n][hw][hw][3]; it is uploaded once and stays on the device.  opt: bs, lr, EPSILON, epoch, init_cost and the
+    recorder's settings (defenses/neural_cleanse/config.py).
+
+    A step is ONE replayed plan -- combat_nc_blend, the eval forward with the head's backward, the input gradient,
+    combat_nc_update -- over device cells (step cursor, Adam step count, cost): an epoch is `steps` replays, one
+    upload (the permutation) before them and one download (the statistics rows) after them."""
+
+    BETAS = (0.5, 0.9)       # detecting.py:151
+    ADAM_EPS = 1e-8          # torch.optim.Adam's default
+
+    def __init__(self, netC, dataset_u8, opt):
+        if getattr(netC, "arch", None) != "preact_resnet18":
+            raise ValueError("NeuralCleanse: only combat_amd.nets.PreActResNet18 is supported (the reference's "
+                             "_get_classifier knows no other classifier for COMBAT's datasets), got %s" % type(netC).__name__)
+        if netC.training:
+            raise ValueError("NeuralCleanse: the classifier must be in eval mode")
+        self.netC, self.opt = netC, opt
+        dev = netC.linear.weight.device
+        data = torch.as_tensor(dataset_u8)
+        if data.dtype != torch.uint8 or data.dim() != 4:
+            raise ValueError("NeuralCleanse: the dataset must be uint8 [n][3][hw][hw] or [n][hw][hw][3], got %s %s"
+                             % (data.dtype, tuple(data.shape)))
+        if data.shape[1] == 3 and data.shape[2] == data.shape[3]:
+            data = data.permute(0, 2, 3, 1)                                   # NCHW -> NHWC, once
+        if data.shape[3] != 3 or data.shape[1] != data.shape[2] or data.shape[1] not in (32, 64, 224):
+            raise ValueError("NeuralCleanse: images must be 32, 64 or 224 pixels square with 3 channels, got %s"
+                             % (tuple(data.shape),))
+        if data.shape[0] < 1:
+            raise ValueError("NeuralCleanse: the dataset is empty")
+        self.data = data.contiguous().to(dev)
+        self.n_data, self.hw = int(data.shape[0]), int(data.shape[1])
+        self.classes = netC.linear.out_features
+        self.bs = int(opt.bs)
+        if self.bs < 1:
+            raise ValueError("NeuralCleanse: bs must be positive")
+        self.steps = (self.n_data + self.bs - 1) // self.bs
+        self.epsilon, self.lr = float(opt.EPSILON), float(opt.lr)
+        hw = self.hw
+        self.params = torch.zeros(4, hw, hw, dtype=torch.float32, device=dev)      # mask_tanh, then pattern_tanh
+        self.mask_tanh, self.pattern_tanh = self.params[0], self.params[1:]
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.cells = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.cursor, self.t = self.cells[0:1], self.cells[1:2]
+        self.cost = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.norm = torch.tensor(NC_MEAN + NC_STD, dtype=torch.float32, device=dev)
+        self.index = torch.zeros(self.n_data, dtype=torch.int32, device=dev)
+        self.stats = torch.zeros(self.steps, 4, dtype=torch.float32, device=dev)
+        self.eng = netC._net_engine()
+        self._plans = {}
+
+    # ---- one step
+    def batch_size(self, step: int) -> int:
+        return min(self.bs, self.n_data - step * self.bs)
+
+    def _parts(self, n: int, target_label: int, grad_out=None):
+        """(slot, blend arguments, forward plan, backward plan, update arguments) of an n-image step.  The head divides by
+        the slot's N rows: loss_weight N / n gives the n real rows 1 / n each (the padding rows' gradients are never read)."""
+        from .engine import pad_batch
+        if not 0 <= int(target_label) < self.classes:
+            raise ValueError("NeuralCleanse: target label %d outside the classifier's %d classes" % (target_label, self.classes))
+        if self.netC.training:
+            raise ValueError("NeuralCleanse: the classifier must be in eval mode")
+        eng = self.eng
+        eng.refresh()
+        N = pad_batch(n)
+        slot = eng.slot("nc", N, self.hw)
+        w = float(N) / n
+        fwd = eng.forward_plan(slot, False, loss_weight=w, head_bwd=True)
+        bwd = eng.backward_eval_plan(slot, w, head_done=True)
+        h = eng.head_bufs(slot)
+        h["targets"].fill_(int(target_label))
+        blend = ops.nc_blend_args(self.data, self.index, self.cursor, self.bs, n, self.mask_tanh, self.pattern_tanh,
+                                  self.epsilon, self.norm, eng.input(slot))
+        update = ops.nc_update_args(slot.bufs["g.img"], self.data, self.index, self.cursor, self.bs, n, h["logits"],
+                                    int(target_label), self.mask_tanh, self.pattern_tanh, self.exp_avg, self.exp_avg_sq,
+                                    self.epsilon, self.norm, self.lr, self.BETAS[0], self.BETAS[1], self.ADAM_EPS, self.t,
+                                    self.cost, self.stats, grad_out)
+        return slot, blend, fwd, bwd, update
+
+    def step_plan(self, n: int, target_label: int, grad_out=None):
+        """The recorded step of an n-image batch towards target_label (one per batch size and label; grad_out, fp32
+        [4][hw][hw], is for tests)."""
+        from .engine import Plan
+        from ._lib import lib
+        key = (n, int(target_label), None if grad_out is None else grad_out.data_ptr())
+        plan = self._plans.get(key)
+        if plan is None:
+            slot, blend, fwd, bwd, update = self._parts(n, target_label, grad_out)
+            for part in (fwd, bwd):     # eval passes: one queue, no marks -- their calls can be re-recorded in line
+                assert not part.aux and not part.after and not part.marks, part.name
+            plan = Plan("nc.step.%d.%d" % (n, target_label))
+            plan.add("nc.blend", lib.combat_nc_blend, *blend)
+            plan.calls += fwd.calls
+            plan.calls += bwd.calls
+            plan.add("nc.update", lib.combat_nc_update, *update)
+            plan.hold(slot, fwd, bwd, grad_out)
+            if len(self._plans) >= 8:                            # a run walks the labels one after the other
+                self._plans.clear()
+            self._plans[key] = plan
+        else:                                                    # what _parts does besides building: operands, head targets
+            self._parts(n, target_label, grad_out)
+        return plan
+
+    def step_eager(self, n: int, target_label: int, grad_out=None) -> None:
+        """The same step as four separate calls (tests compare a replayed plan with it)."""
+        from ._lib import check, lib
+        _, blend, fwd, bwd, update = self._parts(n, target_label, grad_out)
+        st = torch.cuda.current_stream().cuda_stream
+        check(lib.combat_nc_blend(*blend, st), "combat_nc_blend")
+        fwd.run()
+        bwd.run()
+        check(lib.combat_nc_update(*update, st), "combat_nc_update")
+
+    # ---- state
+    def reset(self, init_mask, init_pattern, cost: float = 0.0) -> None:
+        """New parameters, zero moments, Adam's step count and the cursor at 0."""
+        dev = self.params.device
+        self.params[0].copy_(torch.as_tensor(np.asarray(init_mask), dtype=torch.float32).reshape(self.hw, self.hw).to(dev))
+        self.params[1:].copy_(torch.as_tensor(np.asarray(init_pattern), dtype=torch.float32).reshape(3, self.hw, self.hw).to(dev))
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        self.cells.zero_()
+        self.cost.fill_(float(cost))
+
+    def set_index(self, order) -> None:
+        """Upload an epoch's permutation (integers [n_data], checked on the host) and put the cursor at 0."""
+        order = np.asarray(order.cpu() if isinstance(order, torch.Tensor) else order)
+        if order.shape != (self.n_data,) or order.dtype.kind not in "iu" or order.min() < 0 or order.max() >= self.n_data:
+            raise ValueError("NeuralCleanse: the order must hold %d indices into the dataset" % self.n_data)
+        self.index.copy_(torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)))
+        self.cursor.zero_()
+
+    def snapshot(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(raw mask [1][hw][hw], raw pattern [3][hw][hw]) of the current parameters, on the host."""
+        raw = _nc_raw(self.params, self.epsilon).cpu().numpy()
+        return raw[0:1].copy(), raw[1:].copy()
+
+    def run_epoch(self, target_label: int, order, cost: float) -> np.ndarray:
+        """One pass over the dataset in `order` with the L1 weight `cost`: the statistics rows [steps][4] =
+        (loss_ce, correct, loss_reg, n), read back once after the last step."""
+        self.set_index(order)
+        self.cost.fill_(float(cost))
+        tail = self.batch_size(self.steps - 1)
+        full = self.step_plan(self.bs, target_label) if self.steps > 1 or tail == self.bs else None
+        last = full if tail == self.bs else self.step_plan(tail, target_label)
+        for _ in range(self.steps - 1):
+            full.run()
+        last.run()
+        return self.stats.cpu().numpy()
+
+    def optimise(self, target_label: int, init_mask, init_pattern, generator=None, on_best=None,
+                 verbose: bool = True) -> NeuralCleanseRecorder:
+        """detecting.py:143-164 for one label: up to opt.epoch epochs, each over a fresh permutation (the reference's test
+        loader shuffles: one torch.randperm per epoch, from `generator` or torch's global one)."""
+        opt = self.opt
+        rec = NeuralCleanseRecorder(opt, verbose)
+        self.reset(init_mask, init_pattern, rec.cost)
+        for epoch in range(opt.epoch):
+            if verbose:
+                print("Epoch {} - Label: {} | {} - {}:".format(epoch, target_label, getattr(opt, "dataset", ""),
+                                                               getattr(opt, "attack_mode", "")))
+            order = torch.randperm(self.n_data, generator=generator)
+            ce, reg, acc, acc_all = nc_epoch_averages(self.run_epoch(target_label, order, rec.cost))
+            stop = rec.end_epoch(ce, reg, acc, self.snapshot, on_best)
+            if verbose:
+                print("  Result: Accuracy: {:.3f} | Cross Entropy Loss: {:.6f} | Reg Loss: {:.6f} | Reg best: {:.6f}".format(
+                    acc_all, float(ce), float(reg), float(rec.reg_best)))
+            if stop:
+                break
+        return rec

@@ -382,6 +382,65 @@ def strip_entropy(logits, b, s, out) -> None:
           "combat_strip_entropy", "B=%d S=%d classes=%d" % (b, s, logits.shape[1]))
 
 
+def _nc_shapes(what, dataset, index, hw, mask_tanh, pattern_tanh, image_buf, n):
+    """Everything the C side cannot see of a Neural Cleanse launch: the extents behind its pointers."""
+    if tuple(dataset.shape[1:]) != (hw, hw, 3) or dataset.dtype != torch.uint8 or index.dtype != torch.int32:
+        raise ValueError("%s: dataset must be uint8 [n][%d][%d][3] and index int32, got %s %s / %s"
+                         % (what, hw, hw, dataset.dtype, tuple(dataset.shape), index.dtype))
+    if mask_tanh.numel() != hw * hw or pattern_tanh.numel() != 3 * hw * hw or mask_tanh.dtype != torch.float32 \
+            or pattern_tanh.dtype != torch.float32:
+        raise ValueError("%s: mask_tanh / pattern_tanh must be fp32 [%d][%d] / [3][%d][%d]" % (what, hw, hw, hw, hw))
+    if image_buf.dim() != 4 or tuple(image_buf.shape[1:]) != (hw, hw, 8) or image_buf.dtype != bf16 or n > image_buf.shape[0]:
+        raise ValueError("%s: the c8 buffer %s does not hold %d images of %d x %d pixels" % (what, tuple(image_buf.shape), n, hw, hw))
+
+
+def nc_blend_args(dataset, index, cursor, bs, n, mask_tanh, pattern_tanh, epsilon, norm, out_c8):
+    """combat_nc_blend's arguments without the stream (what a Plan records); see nc_blend."""
+    hw = out_c8.shape[1]
+    _nc_shapes("nc_blend", dataset, index, hw, mask_tanh, pattern_tanh, out_c8, n)
+    if norm.numel() != 6 or norm.dtype != torch.float32 or cursor.dtype != torch.int32:
+        raise ValueError("nc_blend: norm must be fp32 [6] (mean, std) and cursor int32 [1]")
+    return (dataset.data_ptr(), dataset.shape[0], index.data_ptr(), index.numel(), cursor.data_ptr(), bs, n, out_c8.shape[0], hw,
+            mask_tanh.data_ptr(), pattern_tanh.data_ptr(), epsilon, norm.data_ptr(), out_c8.data_ptr())
+
+
+def nc_blend(dataset, index, cursor, bs, n, mask_tanh, pattern_tanh, epsilon, norm, out_c8) -> None:
+    """out_c8 rows < n = (1 - m) * x + m * p of the images dataset[index[cursor * bs + i]], rows n.. zero pixels
+    (include/combat_hip.h, combat_nc_blend)."""
+    args = nc_blend_args(dataset, index, cursor, bs, n, mask_tanh, pattern_tanh, epsilon, norm, out_c8)
+    check(lib.combat_nc_blend(*args, _stream()), "combat_nc_blend", "n=%d N=%d hw=%d bs=%d" % (n, out_c8.shape[0], out_c8.shape[1], bs))
+
+
+def nc_update_args(g_img, dataset, index, cursor, bs, n, logits, target_label, mask_tanh, pattern_tanh, exp_avg, exp_avg_sq,
+                   epsilon, norm, lr, beta1, beta2, adam_eps, t, cost, stats, grad_out=None):
+    """combat_nc_update's arguments without the stream (what a Plan records); see nc_update."""
+    hw = g_img.shape[1]
+    _nc_shapes("nc_update", dataset, index, hw, mask_tanh, pattern_tanh, g_img, n)
+    for name, v in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("grad_out", grad_out)):
+        if v is not None and (v.numel() != 4 * hw * hw or v.dtype != torch.float32):
+            raise ValueError("nc_update: %s must be fp32 [4][%d][%d]" % (name, hw, hw))
+    if logits.dim() != 2 or logits.shape[0] < n or logits.dtype != torch.float32 or stats.dim() != 2 or stats.shape[1] != 4 \
+            or stats.dtype != torch.float32:
+        raise ValueError("nc_update: logits must be fp32 [>= n][classes] and stats fp32 [steps][4]")
+    if norm.numel() != 6 or norm.dtype != torch.float32 or cursor.dtype != torch.int32 or t.dtype != torch.int32 \
+            or cost.dtype != torch.float32:
+        raise ValueError("nc_update: norm must be fp32 [6], cursor and t int32 [1], cost fp32 [1]")
+    return (g_img.data_ptr(), dataset.data_ptr(), dataset.shape[0], index.data_ptr(), index.numel(), cursor.data_ptr(), bs, n,
+            g_img.shape[0], hw, logits.data_ptr(), logits.shape[1], target_label, mask_tanh.data_ptr(), pattern_tanh.data_ptr(),
+            exp_avg.data_ptr(), exp_avg_sq.data_ptr(), epsilon, norm.data_ptr(), lr, beta1, beta2, adam_eps, t.data_ptr(),
+            cost.data_ptr(), stats.data_ptr(), stats.shape[0], _p(grad_out))
+
+
+def nc_update(g_img, dataset, index, cursor, bs, n, logits, target_label, mask_tanh, pattern_tanh, exp_avg, exp_avg_sq,
+              epsilon, norm, lr, beta1, beta2, adam_eps, t, cost, stats, grad_out=None) -> None:
+    """The mask / pattern gradients from g_img (channels 0..2) over images < n, Adam on mask_tanh / pattern_tanh, the
+    statistics row stats[cursor], then cursor and t advance (include/combat_hip.h, combat_nc_update)."""
+    args = nc_update_args(g_img, dataset, index, cursor, bs, n, logits, target_label, mask_tanh, pattern_tanh, exp_avg,
+                          exp_avg_sq, epsilon, norm, lr, beta1, beta2, adam_eps, t, cost, stats, grad_out)
+    check(lib.combat_nc_update(*args, _stream()), "combat_nc_update",
+          "n=%d N=%d hw=%d classes=%d target=%d" % (n, g_img.shape[0], g_img.shape[1], logits.shape[1], target_label))
+
+
 def sgd_nesterov(ptrs, sizes, count, max_size, lr, momentum, weight_decay, grad_scale, first_step) -> None:
     check(lib.combat_sgd_nesterov(ptrs.data_ptr(), sizes.data_ptr(), count, max_size, lr, momentum, weight_decay,
                                   grad_scale, int(first_step), _stream()), "combat_sgd_nesterov", "count=%d" % count)

@@ -537,6 +537,58 @@ int combat_strip_superimpose(const void *backgrounds, int32_t B, const void *dat
 int combat_strip_entropy(const float *logits, int32_t B, int32_t S, int32_t classes, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Neural Cleanse defense (defenses/neural_cleanse/detecting.py).  For a target label the reference optimises mask_tanh
+ * [1][hw][hw] and pattern_tanh [3][hw][hw] with Adam over the shuffled test set (:143-164): every mini-batch is blended
+ * with the raw mask and the normalised raw pattern (:27-41), classified, and the cross entropy towards the label plus
+ * cost * |raw mask|_1 is differentiated down to the two parameters (:190-196).  Here a whole optimisation step is
+ *   combat_nc_blend -> the classifier's eval forward and input gradient ('g.img') -> combat_nc_update
+ * recorded once; the step within the epoch, Adam's step count and the cost live in device cells, so the recorded
+ * arguments are the same for every step and the host touches nothing between the first and the last step of an epoch.
+ *
+ * Shared: dataset uint8 [n_data][hw][hw][3] (device resident), index int32 [n_index] (the epoch's permutation), cursor
+ * int32 [1] (step within the epoch): image i of the step is dataset[index[cursor * bs + i]]; an entry beyond n_index or
+ * outside [0, n_data) reads nothing and gives x = 0.  n images of the N rows of the slot are real.  norm fp32 [6] = the
+ * pattern's mean[3], std[3] (:76-78).  With den = 2 + EPSILON (fp32), per pixel (y, x) and channel c:
+ *   x   = (float(u8) / 255.0f - 0.5f) / 0.5f                      (ToTensor's true division, the test loader's Normalize)
+ *   m   = tanhf(mask_tanh[y][x]) / den + 0.5f                     (get_raw_mask, :35-37)
+ *   raw = tanhf(pattern_tanh[c][y][x]) / den + 0.5f               (get_raw_pattern, :39-41)
+ *   p   = y < 3 ? (raw - mean[y]) / std[y] : raw                  (the normalizer, :29-31)
+ * The reference's Normalize.__call__ (networks/models.py:22-26) indexes x[:, channel] of the [3][hw][hw] pattern, which has
+ * no batch axis: the ROW axis.  Rows 0..2 of every colour plane are normalised with mean / std of the row's number and rows
+ * 3.. stay in [0, 1] while the images are in [-1, 1].  Published numbers come from that arithmetic: it is kept.
+ *
+ * combat_nc_blend: out_c8 [N][hw][hw][8] bf16 hi/lo pixels (combat_image_to_c8's layout) of (1 - m) * x + m * p (:32) for
+ * rows < n, zero pixels for rows n..N-1.
+ *
+ * combat_nc_update: g_img bf16 [N][hw][hw][8] (channels 0..2: the loss gradient w.r.t. the blended image; read only, as
+ * is the dataset), logits fp32 [N][classes].  Over the images i < n in a fixed order, without atomics (the same bits
+ * every run):
+ *   gm[y][x]    = sum_i sum_c g_ic * (p_c - x_ic)                  d mask_tanh    = (gm + cost) * (1 - tanh^2) / den
+ *   gp[c][y][x] = (sum_i g_ic) * m / (y < 3 ? std[y] : 1)          d pattern_tanh = gp * (1 - tanh^2) / den
+ * (cost fp32 [1]; the raw mask is positive, so torch.norm(., 1)'s slope is 1, :193-194), written to grad_out fp32
+ * [4][hw][hw] (mask, then the pattern's channels) if it is not NULL.  Then torch.optim.Adam (:151, :196) on the four planes,
+ * moments exp_avg / exp_avg_sq fp32 [4][hw][hw], step count t int32 [1]:  m1 = beta1 * m1 + (1 - beta1) * g,
+ * m2 = beta2 * m2 + (1 - beta2) * g * g,  param -= lr / bc1 * (m1 / (sqrt(m2) / sqrt(bc2) + adam_eps)),
+ * bc = 1 - beta^(t + 1) in fp64; no weight decay, no amsgrad.  stats fp32 [steps][4], row `cursor` = the mini-batch
+ * record of :192-205 over rows < n: mean cross entropy towards target_label, #(argmax == target_label) (the first
+ * maximal class), the sum of the raw mask BEFORE the update, n.  Last, cursor and t advance by one.  A cursor outside
+ * [0, steps) has no row: nothing is written and nothing advances.
+ *
+ * Both: COMBAT_EINVAL for hw not in {32, 64, 224}, n < 0, n > N, N < 1, bs < 1, a negative n_data / n_index, a NULL pointer
+ * (grad_out excepted), cells / dataset / index / logits / stats not 4-byte or parameters, moments, out_c8, g_img not
+ * 16-byte aligned; combat_nc_update also for classes outside 1..16, target_label outside [0, classes), steps < 1.  n == 0
+ * launches nothing and returns COMBAT_OK.
+ * ------------------------------------------------------------------------------------------ */
+int combat_nc_blend(const void *dataset, int32_t n_data, const int32_t *index, int32_t n_index, const int32_t *cursor,
+                    int32_t bs, int32_t n, int32_t N, int32_t hw, const float *mask_tanh, const float *pattern_tanh,
+                    float epsilon, const float *norm, void *out_c8, void *stream);
+int combat_nc_update(const void *g_img, const void *dataset, int32_t n_data, const int32_t *index, int32_t n_index,
+                     int32_t *cursor, int32_t bs, int32_t n, int32_t N, int32_t hw, const float *logits, int32_t classes,
+                     int32_t target_label, float *mask_tanh, float *pattern_tanh, float *exp_avg, float *exp_avg_sq,
+                     float epsilon, const float *norm, float lr, float beta1, float beta2, float adam_eps, int32_t *t,
+                     const float *cost, float *stats, int32_t steps, float *grad_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * SGD(momentum, weight_decay, nesterov) over a list of tensors (train_generator.py:123,125,212,255;
  * torch.optim.SGD semantics: g += wd*p; buf = first ? g : mu*buf + g; p -= lr*(g + mu*buf)).
  * ptrs: DEVICE array of 3*count pointers (param, grad, buf triples); sizes: DEVICE int64[count].
