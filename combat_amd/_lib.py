@@ -134,6 +134,8 @@ SIGNATURES = {
     "combat_nc_update": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32,
                                    c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_i32,
                                    c_vp, c_vp]),
+    "combat_gradcam_seed": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "combat_gradcam_map": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "combat_comm_unique_id": (C.c_int, [c_vp]),
     "combat_comm_init_rank": (C.c_int, [C.POINTER(c_vp), c_i32, c_vp, c_i32]),
     "combat_comm_destroy": (C.c_int, [c_vp]),

@@ -16,7 +16,14 @@ Neural Cleanse (reference defenses/neural_cleanse/detecting.py, neural_cleanse.p
 label a mask and a pattern are optimised with Adam so that every blended test image is classified as the label; the L1
 norms of the masks are compared by their median absolute deviation.  A whole optimisation step -- combat_nc_blend, the
 classifier's eval forward and input gradient, combat_nc_update -- is one replayed plan over device cells (DESIGN.md
-section 10); the recorder, the outlier test and the result file are host code."""
+section 10); the recorder, the outlier test and the result file are host code.
+
+Grad-CAM (reference defenses/gradcam/gradcam.py; Selvaraju et al., ICCV 2017): the map of an image is the ReLU of the
+activations of layer3[1], weighted by the pixel means of the chosen logit's gradient with respect to them, resized to the
+image and stretched to [0, 1].  The reference takes one image at a time through a batch-1 forward, a full backward, two
+host copies, a Python loop over 256 channels and cv2.resize (:162-198); here a batch is one eval forward that keeps the
+tapped block's raw output, combat_gradcam_seed, the input-gradient launches of the blocks behind the tap and
+combat_gradcam_map: nothing but the finished maps leaves the device."""
 from __future__ import annotations
 
 import os
@@ -678,3 +685,189 @@ class NeuralCleanse:
             if stop:
                 break
         return rec
+
+
+# ---------------------------------------------------------------------------------------------- Grad-CAM
+
+
+def _bf16_round(x: np.ndarray) -> np.ndarray:
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.bfloat16).float().numpy()
+
+
+def gradcam_seed_reference(logits, index, W) -> Tuple[np.ndarray, np.ndarray]:
+    """combat_gradcam_seed restated on the host (gradcam.py:168-181 down to the feature map): (chosen int32 [n], d_feat
+    float32 [n][4][4][C] of bf16 values).  chosen[i] = index[i] where index is given and 0 <= index[i] < classes, else the
+    first maximal class of row i -- np.argmax on a row of numbers; a NaN never wins against a number and a row of NaNs
+    gives 0.  d_feat[i][y][x][c] = bf16(W[chosen[i]][c] / 16): d logit / d feat through avgpool(4) and linear."""
+    logits, W = np.asarray(logits, dtype=np.float32), np.asarray(W, dtype=np.float32)
+    n, classes = logits.shape
+    chosen = np.empty(n, dtype=np.int32)
+    for i in range(n):
+        k = -1 if index is None else int(index[i])
+        if not 0 <= k < classes:
+            row, k = logits[i], 0
+            for j in range(1, classes):
+                if row[j] > row[k] or (np.isnan(row[k]) and not np.isnan(row[j])):
+                    k = j
+        chosen[i] = k
+    d = _bf16_round(W[chosen] / np.float32(16.0))
+    return chosen, np.broadcast_to(d[:, None, None, :], (n, 4, 4, W.shape[1])).copy()
+
+
+def _gradcam_taps(f: int, out_hw: int, dtype):
+    """cv2.resize's INTER_LINEAR taps of one axis (its documented geometry): source coordinate (d + 0.5) * f / out_hw - 0.5,
+    i0 = floor, weight of the second neighbour = the fraction; beyond the first or the last cell the border cell alone."""
+    s = (np.arange(out_hw, dtype=dtype) + dtype(0.5)) * (dtype(f) / dtype(out_hw)) - dtype(0.5)
+    fl = np.floor(s)
+    i0, w = fl.astype(np.int64), (s - fl).astype(dtype)
+    w[(i0 < 0) | (i0 >= f - 1)] = 0
+    i0 = np.clip(i0, 0, f - 1)
+    return i0, np.minimum(i0 + 1, f - 1), w
+
+
+def gradcam_resize_reference(r, out_hw: int = 32) -> np.ndarray:
+    """[..., f, f] -> [..., out_hw, out_hw] in r's float dtype: the kernel's bilinear resize,
+    (1 - wy) * ((1 - wx) * r00 + wx * r01) + wy * ((1 - wx) * r10 + wx * r11), with cv2.resize's INTER_LINEAR geometry
+    restated from its documentation (not verified against OpenCV: it is not a dependency)."""
+    r = np.asarray(r)
+    dtype = r.dtype.type if r.dtype in (np.float32, np.float64) else np.float64
+    r = r.astype(dtype, copy=False)
+    f = r.shape[-1]
+    i0, i1, w = _gradcam_taps(f, out_hw, dtype)
+    one = dtype(1)
+    wx, wy = w[None, :], w[:, None]
+    top = (one - wx) * r[..., i0[:, None], i0[None, :]] + wx * r[..., i0[:, None], i1[None, :]]
+    bot = (one - wx) * r[..., i1[:, None], i0[None, :]] + wx * r[..., i1[:, None], i1[None, :]]
+    return (one - wy) * top + wy * bot
+
+
+def gradcam_map_reference(act, grad, dtype=np.float64, out_hw: int = 32) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """combat_gradcam_map restated on the host for act, grad [n][f][f][C] (NHWC): (cam [n][out_hw][out_hw], raw [n][f][f],
+    weights [n][C]) in `dtype`, summed in the kernel's order (include/combat_hip.h): with P = f * f, G = C / 8, L = 256 / G,
+      weights[c] = (sum over l < L of (sum over the pixels l, l + L, ... of grad[p][c])) * (1 / P)
+      raw[p]     = sum over g < G of (the sum over c = 8g .. 8g + 7, from 0, of weights[c] * act[p][c])
+    then r = raw < 0 ? 0 : raw, the resize above, cam = (u - min u) / max(u - min u) -- NaN for a constant map, as
+    gradcam.py:196-197.  dtype=float64 is the reference sum of bf16 inputs (every product exact); dtype=float32 follows the
+    kernel up to its fused multiply-adds, and equals it bit for bit on inputs coarse enough that every partial sum is exact
+    in fp32 (small integers times a power of two, as sweep_reference)."""
+    act, grad = np.asarray(act, dtype=dtype), np.asarray(grad, dtype=dtype)
+    n, f, _, c = act.shape
+    P, G = f * f, c // 8
+    L = 256 // G
+    a, g = act.reshape(n, P, c), grad.reshape(n, P, c)
+    weights = np.zeros((n, c), dtype=dtype)
+    for l in range(L):
+        lane = np.zeros((n, c), dtype=dtype)
+        for p in range(l, P, L):
+            lane = lane + g[:, p]
+        weights = weights + lane
+    weights = weights * dtype(1.0 / P)
+    raw = np.zeros((n, P), dtype=dtype)
+    for k in range(G):
+        s = np.zeros((n, P), dtype=dtype)
+        for ch in range(8 * k, 8 * k + 8):
+            s = s + weights[:, None, ch] * a[:, :, ch]
+        raw = raw + s
+    raw = raw.reshape(n, f, f)
+    u = gradcam_resize_reference(np.where(raw < 0, dtype(0), raw), out_hw)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = u - u.min(axis=(1, 2), keepdims=True)
+        cam = u / u.max(axis=(1, 2), keepdims=True)
+    return cam, raw, weights
+
+
+def gradcam_jet(v) -> np.ndarray:
+    """float32 [..., 3] RGB of values in [0, 1]: the piecewise-linear jet formula, channel = clip(1.5 - |4v - k|, 0, 1) with
+    k = 3, 2, 1 for red, green, blue.  It stands in for OpenCV's COLORMAP_JET table (gradcam.py:325), which is not available
+    here: close to it, not pixel-equal."""
+    v = np.asarray(v, dtype=np.float32)[..., None]
+    return np.clip(np.float32(1.5) - np.abs(np.float32(4.0) * v - np.array([3.0, 2.0, 1.0], dtype=np.float32)), 0.0, 1.0)
+
+
+def gradcam_overlay(img_u8_hwc, cam) -> Tuple[np.ndarray, np.ndarray]:
+    """(heat map uint8 [hw][hw][3], overlay uint8 [hw][hw][3]), both RGB, with show_cam_on_image's arithmetic
+    (gradcam.py:324-332): the colour map of uint8(255 * cam), heatmap / 255 + img / 255 in fp32, divided by its maximum,
+    uint8(255 * .).  A NaN map (a constant one) counts as zero.  The reference adds an RGB image to OpenCV's BGR heat map,
+    so its files have the picture's red and blue swapped; here both are RGB."""
+    cam = np.nan_to_num(np.asarray(cam, dtype=np.float32), nan=0.0)
+    level = np.uint8(np.float32(255) * np.clip(cam, 0.0, 1.0))
+    heatmap_u8 = np.uint8(np.rint(np.float32(255) * gradcam_jet(level.astype(np.float32) / np.float32(255))))
+    mix = heatmap_u8.astype(np.float32) / np.float32(255) + np.asarray(img_u8_hwc).astype(np.float32) / np.float32(255)
+    mix = mix / np.max(mix)
+    return heatmap_u8, np.uint8(np.float32(255) * mix)
+
+
+class GradCam:
+    """maps() of a batch of images under the classifier `netC` (a combat_amd.nets PreActResNet18 for 32 x 32 inputs, in eval
+    mode).  target_block: the pre-activation block whose raw output is tapped, 0..6 in network order; 5 is layer3[1], the
+    reference's choice (gradcam.py:377)."""
+
+    def __init__(self, netC, target_block: int = 5):
+        if getattr(netC, "arch", None) != "preact_resnet18":
+            raise ValueError("GradCam: only combat_amd.nets.PreActResNet18 is supported (the reference's get_model knows "
+                             "no other classifier), got %s" % type(netC).__name__)
+        if netC.training:
+            raise ValueError("GradCam: the classifier must be in eval mode")
+        self.C = netC.layer4[1].conv2.out_channels
+        if netC.linear.in_features != self.C:
+            raise ValueError("GradCam: only the 32 x 32 classifier is supported (linear.in_features %d, layer4 has %d channels)"
+                             % (netC.linear.in_features, self.C))
+        if isinstance(target_block, bool) or int(target_block) != target_block or not 0 <= int(target_block) <= 6:
+            raise ValueError("GradCam: target_block %r outside 0..6" % (target_block,))
+        self.netC, self.target_block = netC, int(target_block)
+        self.classes = netC.linear.out_features
+        self.hw = 32
+        self.eng = netC._net_engine()
+
+    def _index(self, index, n: int, dev) -> Optional[torch.Tensor]:
+        """int32 [n] on the device; a host index is range-checked here, before the upload (-1: the row's argmax)."""
+        if index is None:
+            return None
+        if isinstance(index, torch.Tensor) and index.is_cuda:
+            if index.dim() != 1 or index.numel() != n or index.dtype.is_floating_point or index.dtype == torch.bool:
+                raise ValueError("maps: index must be integers [n = %d], got %s %s" % (n, index.dtype, tuple(index.shape)))
+            return index.to(device=dev, dtype=torch.int32).contiguous()
+        idx = np.asarray(index.numpy() if isinstance(index, torch.Tensor) else index)
+        if idx.shape != (n,) or idx.dtype.kind not in "iu":
+            raise ValueError("maps: index must be integers [n = %d], got %s %s" % (n, idx.dtype, idx.shape))
+        if n and (idx.min() < -1 or idx.max() >= self.classes):
+            raise ValueError("maps: index outside -1 (the row's argmax) .. %d" % (self.classes - 1))
+        return torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(dev)
+
+    def tapped(self, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(activations, gradient) bf16 [N][f][f][C] of the last maps() call of n images: the engine's buffers themselves."""
+        from .engine import pad_batch
+        slot = self.eng.slot("gradcam", pad_batch(n), self.hw)
+        return slot.bufs["b%d.out" % self.target_block], slot.bufs["g.b%d.dx" % (self.target_block + 1)]
+
+    @torch.no_grad()
+    def maps(self, inputs: torch.Tensor, index=None, raw_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(cam fp32 [n][32][32], chosen int32 [n]) on the device for a float32 NCHW device batch in [-1, 1].  index:
+        the class whose logit is explained, per image (host or device integers [n]; -1 or None: the image's first maximal
+        logit).  A map that is constant (nowhere positive before the ReLU, say) is NaN, as the reference's: test with isnan.
+        raw_out (fp32 [n][f][f]) receives the map before ReLU and resize.  Nothing in here waits for the device."""
+        from .engine import pad_batch
+        if self.netC.training:
+            raise ValueError("maps: the classifier must be in eval mode")
+        if not isinstance(inputs, torch.Tensor) or inputs.dim() != 4 or tuple(inputs.shape[1:]) != (3, self.hw, self.hw) \
+                or inputs.dtype != torch.float32 or not inputs.is_cuda:
+            raise ValueError("maps: inputs must be a float32 device batch [n][3][%d][%d], got %s"
+                             % (self.hw, self.hw, (inputs.dtype, tuple(inputs.shape)) if isinstance(inputs, torch.Tensor) else type(inputs)))
+        n, dev = inputs.shape[0], inputs.device
+        idx = self._index(index, n, dev)
+        cam = torch.empty(n, 32, 32, dtype=torch.float32, device=dev)
+        if n == 0:
+            return cam, torch.empty(0, dtype=torch.int32, device=dev)
+        eng, b = self.eng, self.target_block
+        eng.refresh()
+        N = pad_batch(n)
+        slot = eng.slot("gradcam", N, self.hw)
+        ops.image_to_c8(inputs.contiguous(), eng.input(slot))
+        eng.forward_plan(slot, False, keep_raw_blocks=(b,)).run()
+        chosen = torch.empty(N, dtype=torch.int32, device=dev)
+        d_feat = slot.buf("g.feat", (N, 4, 4, self.C))
+        ops.gradcam_seed(eng.head_bufs(slot)["logits"], idx, n, eng.lin_w, chosen, d_feat)
+        eng.backward_eval_plan(slot, 1.0, head_done=True, stop_before=b + 1).run()
+        act, grad = self.tapped(n)
+        ops.gradcam_map(act, grad, n, cam, raw_out)
+        return cam, chosen[:n]

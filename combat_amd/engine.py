@@ -978,7 +978,7 @@ class PreActEngine(NetEngine):
         "b%d.%s" % (b, s) for b in range(8) for s in ("y1", "out", "sc", "a1", "act")) + ("stem.act",)
 
     def forward_plan(self, slot: Slot, train: bool, loss_weight: float = 1.0, with_targets2: bool = False,
-                     split_head: bool = False, head_bwd: bool = False, two_loss: bool = False) -> Plan:
+                     split_head: bool = False, head_bwd: bool = False, two_loss: bool = False, keep_raw_blocks=()) -> Plan:
         """split_head (eval only): the batch is two independent halves [metric-only images ; images whose
         loss is differentiated]; the head runs once per half with separate loss / counter cells
         (first half -> correct[0] of slot 'loss0/correct0' cells, second half -> the usual ones).
@@ -989,7 +989,15 @@ class PreActEngine(NetEngine):
         'loss1' / 'correct1'; the matching backward is backward_eval_plan(half_weights=...).  Each half runs as the
         n-image plan over views of this slot's input, head and 'g.img' buffers (two_loss_halves): the results are
         those of two separate n-image passes, bit for bit -- a 2n-image plan picks other tile / partition
-        parameters and rounds differently."""
+        parameters and rounds differently.
+        keep_raw_blocks (eval only, PreActEngine only): blocks whose raw output 'b%d.out' is written although no identity
+        shortcut reads it (Grad-CAM taps it, combat_amd/defenses.py::GradCam); everything else is computed as without."""
+        keep_raw_blocks = tuple(sorted(set(int(b) for b in keep_raw_blocks)))
+        if keep_raw_blocks:
+            if type(self) is not PreActEngine or train or two_loss:
+                raise ValueError("keep_raw_blocks: only an eval pass of the pre-activation classifier keeps extra raw outputs")
+            if keep_raw_blocks[0] < 0 or keep_raw_blocks[-1] >= len(self.blocks):
+                raise ValueError("keep_raw_blocks: blocks %s outside 0..%d" % (keep_raw_blocks, len(self.blocks) - 1))
         if two_loss:
             assert not train and not split_head and not with_targets2 and not head_bwd
             key = "fwd.eval.%g.tl" % loss_weight
@@ -1000,12 +1008,16 @@ class PreActEngine(NetEngine):
                 slot.feat_hw = halves[0].feat_hw
             return slot.plans[key]
         key = "fwd.%s.%g.%d.%d%s" % ("train" if train else "eval", loss_weight, with_targets2, split_head, ".hb" if head_bwd else "")
+        if keep_raw_blocks:
+            key += ".kr" + ",".join(str(b) for b in keep_raw_blocks)
         if key in slot.plans:
             return slot.plans[key]
         P = Plan("preact." + key)
         n, hw = slot.N, slot.hw
         x = self.input(slot)
-        if not train:
+        if keep_raw_blocks:
+            cur, chw = self._forward_eval_body(P, slot, x, keep_raw_blocks)
+        elif not train:
             cur, chw = self._forward_eval_body(P, slot, x)
         else:
             cur, chw = self._forward_train_body(P, slot, x)
@@ -1106,13 +1118,13 @@ class PreActEngine(NetEngine):
             cur, chw = out, ohw
         return cur, chw
 
-    def _forward_eval_body(self, P: Plan, slot: Slot, x):
+    def _forward_eval_body(self, P: Plan, slot: Slot, x, keep_raw_blocks=()):
         """Eval mode: every BatchNorm is a fixed per-channel affine known before its producer runs, so the
         producing convolution writes relu(bn(.)) itself (second epilogue output) and no convolution
         needs a prologue -- the 3x3 / stride-1 layers then run on the DMA-staged kernel.  Tensors:
         'stem.act' / 'b%d.act' = relu(bn1_next(block output)), 'b%d.a1' = relu(bn2(conv1 output));
         the raw block output ('stem' / 'b%d.out') is kept only where an identity shortcut or the head
-        reads it."""
+        reads it, or the caller names the block in keep_raw_blocks."""
         n, hw = slot.N, slot.hw
         blocks = self.blocks
         raw = slot.buf("stem", (n, hw, hw, 64)) if blocks[0].sc is None else None
@@ -1132,7 +1144,7 @@ class PreActEngine(NetEngine):
             if blk.sc is not None:
                 P.merge_convs(len(P.calls) - 2)
             nxt = blocks[b + 1] if b + 1 < len(blocks) else None
-            keep_raw = nxt is None or nxt.sc is None
+            keep_raw = nxt is None or nxt.sc is None or b in keep_raw_blocks
             out = slot.buf("b%d.out" % b, shape) if keep_raw else None
             if nxt is not None:
                 nact = slot.buf("b%d.act" % b, shape)
@@ -1243,16 +1255,25 @@ class PreActEngine(NetEngine):
                                                                                             half_weights)])
         return slot.plans[key]
 
-    def backward_eval_plan(self, slot: Slot, loss_weight: float, head_done: bool = False, half_weights=None) -> Plan:
+    def backward_eval_plan(self, slot: Slot, loss_weight: float, head_done: bool = False, half_weights=None,
+                           stop_before: Optional[int] = None) -> Plan:
         """Backward of an eval-mode forward w.r.t. the input image only (Phase G: the classifier
         and clean-model weight gradients are never consumed, train_generator.py:179,254).
         Result: slot buffer 'g.img' (bf16 NHWC c8, channels 0..2).  head_done: as backward_train_plan.
         half_weights (w0, w1): the backward of a two_loss forward -- each half's mean loss with its weight (loss_weight
-        is then unused), each half through its n-image plan."""
+        is then unused), each half through its n-image plan.
+        stop_before b: the plan ends after block b's input-gradient launch and runs no stem dgrad.  Result: 'g.b%d.dx' % b,
+        the gradient w.r.t. the RAW output of block b - 1 ('b%d.out' % (b - 1); the stem's for b == 0): that launch applies
+        block b's bn1 scale and ReLU mask, adds the shortcut's gradient before the mask and the identity path after it."""
         if half_weights is not None:
-            assert not head_done
+            assert not head_done and stop_before is None
             return self._two_loss_backward(slot, half_weights)
         key = "bwd.eval.%g%s" % (loss_weight, ".hd" if head_done else "")
+        if stop_before is not None:
+            if not 0 <= int(stop_before) < len(self.blocks):
+                raise ValueError("stop_before: block %s outside 0..%d" % (stop_before, len(self.blocks) - 1))
+            stop_before = int(stop_before)
+            key += ".sb%d" % stop_before
         if key in slot.plans:
             return slot.plans[key]
         P = Plan("preact." + key)
@@ -1283,6 +1304,9 @@ class PreActEngine(NetEngine):
                      mask=blk.bn1.eval_affine(), mask_mul_scale=True, mask_activated=True,
                      add_post=None if blk.sc is not None else d_out)
             d_out = dxin
+            if b == stop_before:
+                slot.plans[key] = P
+                return P
         gimg = slot.buf("g.img", (n, slot.hw, slot.hw, 8))
         rec_conv(P, "stem.dgrad", d_out, gimg, self.stem, 1)
         slot.plans[key] = P

@@ -441,6 +441,41 @@ def nc_update(g_img, dataset, index, cursor, bs, n, logits, target_label, mask_t
           "n=%d N=%d hw=%d classes=%d target=%d" % (n, g_img.shape[0], g_img.shape[1], logits.shape[1], target_label))
 
 
+def gradcam_seed(logits, index, n, weight, chosen, d_feat) -> None:
+    """chosen[i] = index[i] (>= 0) or the row's first maximal class, d_feat[i] = bf16(weight[chosen[i]] / 16) on all 16
+    pixels, for rows < n; rows n.. get -1 and zeros (include/combat_hip.h, combat_gradcam_seed).  An index on the host
+    would have been range-checked by the caller (defenses.GradCam.maps); the kernel reads an entry >= classes as -1."""
+    N, classes = logits.shape
+    c = weight.shape[1]
+    if logits.dtype != torch.float32 or weight.dtype != torch.float32 or weight.shape[0] != classes or not weight.is_contiguous():
+        raise ValueError("gradcam_seed: logits must be fp32 [N][classes] and weight fp32 [classes][C], got %s %s / %s %s"
+                         % (logits.dtype, tuple(logits.shape), weight.dtype, tuple(weight.shape)))
+    if chosen.dtype != torch.int32 or chosen.numel() < N or d_feat.dtype != bf16 or tuple(d_feat.shape) != (N, 4, 4, c):
+        raise ValueError("gradcam_seed: chosen must be int32 [N = %d] and d_feat bf16 [%d][4][4][%d], got %s %s / %s %s"
+                         % (N, N, c, chosen.dtype, tuple(chosen.shape), d_feat.dtype, tuple(d_feat.shape)))
+    if index is not None and (index.dtype != torch.int32 or index.numel() < n):
+        raise ValueError("gradcam_seed: index must be int32 [>= n = %d], got %s %s" % (n, index.dtype, tuple(index.shape)))
+    check(lib.combat_gradcam_seed(logits.data_ptr(), _p(index), n, N, classes, c, weight.data_ptr(), chosen.data_ptr(),
+                                  d_feat.data_ptr(), _stream()),
+          "combat_gradcam_seed", "n=%d N=%d classes=%d C=%d" % (n, N, classes, c))
+
+
+def gradcam_map(act, grad, n, cam, raw=None, weights=None) -> None:
+    """cam (fp32 [n][32][32]) of the first n images of act / grad (bf16 [>= n][f][f][C]); raw fp32 [n][f][f] (the map
+    before ReLU) and weights fp32 [n][C] if given (include/combat_hip.h, combat_gradcam_map)."""
+    if act.dim() != 4 or act.shape != grad.shape or act.dtype != bf16 or grad.dtype != bf16 or act.shape[1] != act.shape[2] \
+            or act.shape[0] < n or not act.is_contiguous() or not grad.is_contiguous():
+        raise ValueError("gradcam_map: act and grad must be contiguous bf16 [>= n = %d][f][f][C] of one shape, got %s %s / %s %s"
+                         % (n, act.dtype, tuple(act.shape), grad.dtype, tuple(grad.shape)))
+    f, c = act.shape[1], act.shape[3]
+    for name, v, size in (("cam", cam, n * 32 * 32), ("raw", raw, n * f * f), ("weights", weights, n * c)):
+        if v is not None and (v.dtype != torch.float32 or v.numel() < size or not v.is_contiguous()):
+            raise ValueError("gradcam_map: %s must be contiguous fp32 with at least %d elements, got %s %s"
+                             % (name, size, v.dtype, tuple(v.shape)))
+    check(lib.combat_gradcam_map(act.data_ptr(), grad.data_ptr(), n, f, c, 32, cam.data_ptr(), _p(raw), _p(weights), _stream()),
+          "combat_gradcam_map", "n=%d f=%d C=%d" % (n, f, c))
+
+
 def sgd_nesterov(ptrs, sizes, count, max_size, lr, momentum, weight_decay, grad_scale, first_step) -> None:
     check(lib.combat_sgd_nesterov(ptrs.data_ptr(), sizes.data_ptr(), count, max_size, lr, momentum, weight_decay,
                                   grad_scale, int(first_step), _stream()), "combat_sgd_nesterov", "count=%d" % count)

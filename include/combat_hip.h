@@ -589,6 +589,50 @@ int combat_nc_update(const void *g_img, const void *dataset, int32_t n_data, con
                      const float *cost, float *stats, int32_t steps, float *grad_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Grad-CAM defense (defenses/gradcam/gradcam.py).  For one image the reference runs a batch-1 forward with a hook on
+ * layer3[1], builds a one-hot of the chosen class, backpropagates sum(one_hot * output) through the whole network
+ * (:168-181), copies the hooked activations and their gradient to the host and, in numpy, averages the gradient over the
+ * pixels, sums the weighted channels in a Python loop, applies ReLU, cv2.resize to 32 x 32 and stretches to [0, 1]
+ * (:183-197).  Here a batch is
+ *   the eval forward with the tapped block's raw output kept -> combat_gradcam_seed -> the input-gradient launches down to
+ *   the tapped block -> combat_gradcam_map
+ * and only the finished maps leave the device.
+ *
+ * combat_gradcam_seed (replaces :168-181 down to the feature map): logits fp32 [N][classes], index int32 [N] or NULL, n
+ * real rows of the slot's N, W fp32 [classes][C] (linear.weight; the 32 x 32 classifier only: a 4 x 4 feature map under
+ * avgpool(4), linear.in_features == C).  Row i < n:  k = index[i] if index != NULL and 0 <= index[i] < classes, otherwise
+ * the first maximal class of the row (np.argmax on a row of numbers; a NaN never wins against a number, a row of NaNs
+ * gives 0);  chosen[i] = k;  d_feat[i][y][x][c] = bf16(W[k][c] / 16.0f) for the 16 pixels -- d logit_k / d feat, the
+ * engine's 'g.feat' buffer, bf16 [N][4][4][C].  Rows n..N-1: chosen = -1, zero gradients.  COMBAT_EINVAL for classes
+ * outside 1..16, C < 8 or not a multiple of 8, n < 0, n > N, N < 1, a NULL pointer other than index, logits / index / W /
+ * chosen not 4-byte or d_feat not 16-byte aligned (what combat_head_bwd's kernels assume of the same buffers); n == 0
+ * launches nothing.  (The Python binding refuses a host index >= classes before the upload.)
+ *
+ * combat_gradcam_map (replaces :183-197): act, grad bf16 [>= n][f][f][C] (the tapped block's raw output and the gradient
+ * with respect to it), f in {4, 8, 16, 32}, C in {64, 128, 256, 512}, out_hw == 32.  One workgroup of 256 threads per
+ * image; all sums fp32 in this fixed order, no atomics (the same bits every run).  With P = f * f pixels p = y * f + x,
+ * G = C / 8 and L = 256 / G:
+ *   weights[c] = (sum over l = 0..L-1, in order, of (sum over the pixels p = l, l + L, l + 2L, ... < P, in order, of
+ *                grad[p][c])) * (1.0f / P)                                             (np.mean(grads_val, axis=(2, 3)))
+ *   raw[p]     = sum over g = 0..G-1, in order, of s_g,   s_g = fmaf chain  s = fmaf(weights[c], act[p][c], s)  from
+ *                s = 0 over c = 8g .. 8g + 7                                             (the loop cam += w * target[i])
+ *   r          = raw < 0 ? 0 : raw                                                       (np.maximum(cam, 0))
+ *   u[dy][dx]  = (1 - wy) * ((1 - wx) * r[y0][x0] + wx * r[y0][x1]) + wy * ((1 - wx) * r[y1][x0] + wx * r[y1][x1])
+ *                with cv2.resize's INTER_LINEAR geometry per axis: s = (d + 0.5f) * f / 32 - 0.5f, i0 = floor(s),
+ *                w = s - i0; i0 < 0: i0 = 0, w = 0; i0 >= f - 1: i0 = f - 1, w = 0; i1 = min(i0 + 1, f - 1)
+ *                (f == 32: the identity)
+ *   cam        = (u - min u) / (max u - min u)        a true fp32 division; max(u - min u) == max u - min u bit for bit
+ * cam fp32 [n][32][32]; raw fp32 [n][f][f] and weights fp32 [n][C] are written if not NULL.  A constant map (an image whose
+ * raw map is nowhere positive, say) gives 0 / 0 = NaN in every pixel, as the reference's cam / np.max(cam) does; a NaN in
+ * raw spreads to the whole map as np.min / np.max spread it.  COMBAT_EINVAL for f, C outside the sets, out_hw != 32,
+ * n < 0, a NULL act / grad / cam, act / grad not 16-byte or cam / raw / weights not 4-byte aligned; n == 0 launches nothing.
+ * ------------------------------------------------------------------------------------------ */
+int combat_gradcam_seed(const float *logits, const int32_t *index, int32_t n, int32_t N, int32_t classes, int32_t C,
+                        const float *W, int32_t *chosen, void *d_feat, void *stream);
+int combat_gradcam_map(const void *act, const void *grad, int32_t n, int32_t f, int32_t C, int32_t out_hw, float *cam,
+                       float *raw, float *weights, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * SGD(momentum, weight_decay, nesterov) over a list of tensors (train_generator.py:123,125,212,255;
  * torch.optim.SGD semantics: g += wd*p; buf = first ? g : mu*buf + g; p -= lr*(g + mu*buf)).
  * ptrs: DEVICE array of 3*count pointers (param, grad, buf triples); sizes: DEVICE int64[count].
