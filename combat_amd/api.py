@@ -16,15 +16,25 @@ def _c(hw: int, ratio: float, device):
     return _consts[key]
 
 
-def create_backdoor(netG, inputs: torch.Tensor, opt, sigma: float = None, noise_from: torch.Tensor = None) -> torch.Tensor:
+def create_backdoor(netG, inputs: torch.Tensor, opt, sigma: float = None, noise_from: torch.Tensor = None,
+                    labels: torch.Tensor = None) -> torch.Tensor:
     """netG -> low_freq -> clamp(x + noise*rate) -> GaussianBlur (one sigma per call, drawn here from
     torch's global generator like T.GaussianBlur) for a float32 NCHW device batch; no gradient.
     noise_from: a batch of the same shape whose generator noise is mixed onto `inputs` instead of their own -- the
-    input-aware attack's cross images (train_generator_inputaware.py:236-238, 412-414)."""
+    input-aware attack's cross images (train_generator_inputaware.py:236-238, 412-414).
+    labels: the classes a label-conditioned generator (nets.CUnetGeneratorv1) poisons the images towards, one per image
+    (create_inputs_bd(inputs, targets, netG, opt), train_generator_multilabel.py:67-75); required for it, refused for
+    every other generator."""
     n, _, hw, _ = inputs.shape
     if noise_from is not None and tuple(noise_from.shape) != tuple(inputs.shape):
         raise ValueError("create_backdoor: noise_from %s must have the shape of inputs %s"
                          % (tuple(noise_from.shape), tuple(inputs.shape)))
+    if (labels is not None) != (netG.arch == "cunet"):
+        raise ValueError("create_backdoor: labels are %s" % ("required by a label-conditioned generator" if labels is None
+                                                             else "taken by a label-conditioned generator only"))
+    if labels is not None:
+        from .engine import check_labels
+        labels = check_labels(labels, n, netG.num_classes)
     if n == 0:
         return inputs
     eng = netG._net_engine()
@@ -42,6 +52,8 @@ def create_backdoor(netG, inputs: torch.Tensor, opt, sigma: float = None, noise_
     from .engine import pad_batch
     slot = eng.slot("api", pad_batch(n), hw)
     ops.image_to_c8(inputs if noise_from is None else noise_from.contiguous().float(), eng.input(slot))
+    if labels is not None:
+        eng.labels(slot)[:n].copy_(labels)
     eng.forward_plan(slot).run()
     if sigma is None:
         sigma = trigger.sample_sigma(getattr(opt, "sigma", (0.1, 1.0)))

@@ -313,6 +313,34 @@ __global__ __launch_bounds__(256) void trigger_pair_bwd_kernel(const float *__re
                              cross ? 0.f : l2_scale, 0.f, pre_tanh, d_noise + (long)row * hw2 * 8);
 }
 
+// The grouped trigger of the multi-label step (train_generator_multilabel.py:203-224): the batch is cut into chunks of
+// `ps` images, one target class and one draw of the blur each.  Image i is blurred with k1[i / ps] (the last group may be
+// short).  Per image the same body as trigger_fwd_kernel / trigger_bwd_kernel, so the results are those of one call of
+// them per chunk.
+__global__ __launch_bounds__(256) void trigger_groups_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                                 const float *__restrict__ P, const float *__restrict__ k1,
+                                                                 float rate, int hw, int ps, float *__restrict__ out,
+                                                                 float *__restrict__ mse) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.x, img = blockIdx.y;
+    trigger_fwd_plane<false>(sm, x + ((long)img * 3 + c) * hw2, noise + (long)img * hw2 * 8, P, k1 + 3 * (img / ps), rate, hw,
+                             c, img, out + ((long)img * 3 + c) * hw2, nullptr, mse, nullptr);
+}
+
+__global__ __launch_bounds__(256) void trigger_groups_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                                 const float *__restrict__ P, const float *__restrict__ k1,
+                                                                 float rate, int hw, int ps, const float *__restrict__ d_out,
+                                                                 const float *__restrict__ d_out2,
+                                                                 const float *__restrict__ outp, float l2_scale,
+                                                                 int pre_tanh, __bf16 *__restrict__ d_noise) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.x, img = blockIdx.y;
+    const long pl = ((long)img * 3 + c) * hw2;
+    trigger_bwd_plane<false>(sm, x + pl, noise + (long)img * hw2 * 8, P, k1 + 3 * (img / ps), rate, hw, c,
+                             d_out ? d_out + pl : nullptr, d_out2 ? d_out2 + pl : nullptr, outp ? outp + pl : nullptr, l2_scale,
+                             0.f, pre_tanh, d_noise + (long)img * hw2 * 8);
+}
+
 // ------------------------------------------------------------------ augmentation
 struct AugGeom {
     float ca, sa, cx, cy;
@@ -669,6 +697,38 @@ extern "C" int combat_trigger_pair_bwd(const float *x, const void *noise, const 
     COMBAT_LAUNCH(trigger_pair_bwd_kernel, dim3(3, 2 * n), dim3(256), bytes, as_stream(stream), x,
                        reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, n, hw, d_bd, d_bd2, out_bd, l2_scale,
                        d_cross, pre_tanh, reinterpret_cast<__bf16 *>(d_noise));
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+
+extern "C" int combat_trigger_groups_fwd(const float *x, const void *noise, const float *P, const float *k1,
+                                         float noise_rate, int32_t n, int32_t hw, int32_t ps, float *out,
+                                         float *mse_partial, void *stream) {
+    COMBAT_PLAN_HOOK(combat_trigger_groups_fwd, x, noise, P, k1, noise_rate, n, hw, ps, out, mse_partial);
+    if (!x || !noise || !P || !k1 || !out || n < 0 || ps < 1 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (n == 0) return COMBAT_OK;
+    const int bytes = (4 * hw * hw + 2 * hw) * 4;
+    if (set_smem(trigger_groups_fwd_kernel, bytes)) return COMBAT_ELAUNCH;
+    COMBAT_LAUNCH(trigger_groups_fwd_kernel, dim3(3, n), dim3(256), bytes, as_stream(stream), x,
+                       reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, ps, out, mse_partial);
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+
+extern "C" int combat_trigger_groups_bwd(const float *x, const void *noise, const float *P, const float *k1,
+                                         float noise_rate, int32_t n, int32_t hw, int32_t ps, const float *d_out,
+                                         const float *d_out2, const float *out, float l2_scale, int32_t pre_tanh,
+                                         void *d_noise, void *stream) {
+    COMBAT_PLAN_HOOK(combat_trigger_groups_bwd, x, noise, P, k1, noise_rate, n, hw, ps, d_out, d_out2, out, l2_scale, pre_tanh,
+                     d_noise);
+    if (!x || !noise || !P || !k1 || !d_noise || n < 0 || ps < 1 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (l2_scale != 0.f && !out) return COMBAT_EINVAL;
+    if (n == 0) return COMBAT_OK;
+    const int bytes = (5 * hw * hw + 2 * hw) * 4;
+    if (set_smem(trigger_groups_bwd_kernel, bytes)) return COMBAT_ELAUNCH;
+    COMBAT_LAUNCH(trigger_groups_bwd_kernel, dim3(3, n), dim3(256), bytes, as_stream(stream), x,
+                       reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, ps, d_out, d_out2, out, l2_scale,
+                       pre_tanh, reinterpret_cast<__bf16 *>(d_noise));
     CB_LAUNCH_CHECK();
     return COMBAT_OK;
 }

@@ -1568,12 +1568,25 @@ class UnetEngine(NetEngine):
         self.bias: Dict[str, torch.Tensor] = {}
         for name, ci, co, stride, _ in UNET_LAYERS:
             conv = getattr(m, name)
-            cin_pad = 8 if ci == 0 else conv.in_channels
-            self.pc[name] = self._pc(conv.weight.data, stride, 1, cin_pad, dup=(ci == 0), need_dgrad=(ci != 0))
+            weight, cin = self._conv_operand(name, conv)
+            cin_pad = 8 if ci == 0 else cin
+            self.pc[name] = self._pc(weight, stride, 1, cin_pad, dup=(ci == 0), need_dgrad=(ci != 0))
             self.bias[name] = conv.bias.data if conv.bias is not None else None
         self.out_bias8 = torch.zeros(8, dtype=f32, device=self.device)
         self.ones = torch.ones(64 * 8, dtype=f32, device=self.device)
         self.zeros = torch.zeros(64 * 8, dtype=f32, device=self.device)
+
+    def _conv_operand(self, name: str, conv):
+        """(fp32 master weight, input channels) the packed operand of layer `name` is built from."""
+        return conv.weight.data, conv.in_channels
+
+    def _cond_forward(self, P: Plan, slot: Slot, s: int) -> dict:
+        """Extra arguments of conv0_1's forward launch (CUnetEngine: the label term); records what produces them."""
+        return {}
+
+    def _conv0_1_wgrad(self, P: Plan, slot: Slot, d) -> None:
+        """The weight gradient of conv0_1 from d, the gradient w.r.t. its raw output."""
+        rec_wgrad(P, "conv0_1.wgrad", slot.bufs["a.conv0_1"], d, self.pc["conv0_1"], self.fp.grad_phys("conv0_1.weight"))
 
     def _refresh_extra(self):
         if self.bias8_taken:          # the caller copied it with its own small copies (small_refresh_copy)
@@ -1619,7 +1632,7 @@ class UnetEngine(NetEngine):
         rec_conv(P, "conv0_0", x, t00, pc["conv0_0"], 0, bias=bs["conv0_0"], act_dst=a01,
                  act=Affine(self.ones, self.zeros, 0, True, self.LR))
 
-        def cn(name, src, s, c, pro, defer=False):
+        def cn(name, src, s, c, pro, defer=False, **conv_kw):
             # pro: None (src is used as is), an Affine (activation only), or the NormState of src whose
             # finalize was deferred to here.  No bias: InstanceNorm removes any per-(image, channel) constant, so
             # IN(conv(x) + b) == IN(conv(x)) exactly, and leaving b out keeps the stored bf16
@@ -1632,11 +1645,11 @@ class UnetEngine(NetEngine):
                 else:
                     rec_act(P, name + ".act", src, act, pro)
                 src = act
-            st = self._conv_norm(P, slot, name, src, dst, pc[name], groups=n, defer=defer)
+            st = self._conv_norm(P, slot, name, src, dst, pc[name], groups=n, defer=defer, **conv_kw)
             return dst, st
 
         # defer=True: the layer's InstanceNorm is finalised by the launch that writes the next conv's input
-        t01, s01 = cn("conv0_1", a01, h1, nf, None, True)
+        t01, s01 = cn("conv0_1", a01, h1, nf, None, True, **self._cond_forward(P, slot, h1))
         t10, s10 = cn("conv1_0", t01, h2, nf * 2, s01, True)
         t11, s11 = cn("conv1_1", t10, h2, nf * 2, s10, True)
         t20, s20 = cn("conv2_0", t11, h3, nf * 4, s11, True)
@@ -1760,7 +1773,7 @@ class UnetEngine(NetEngine):
         # conv0_1 reads LeakyReLU(conv0_0 output): no norm in between
         t00 = t("conv0_0")
         lr_only = Affine(None, None, 0, True, self.LR)
-        rec_wgrad(P, "conv0_1.wgrad", slot.bufs["a.conv0_1"], d, pc["conv0_1"], fp.grad_phys("conv0_1.weight"))
+        self._conv0_1_wgrad(P, slot, d)
         d00 = G("conv0_0.dx", t00)
         rec_conv(P, "conv0_1.dgrad", d, d00, pc["conv0_1"], 1, mask_x=t00, mask=Affine(None, None, 0, True, self.LR))
         P.add("db.conv0_0", lib.combat_colsum, d00.data_ptr(), d00.numel() // d00.shape[-1], d00.shape[-1],
@@ -1770,6 +1783,69 @@ class UnetEngine(NetEngine):
         balance_wgrads(P, self.device)
         slot.plans["bwd"] = P
         return P
+
+
+class CUnetEngine(UnetEngine):
+    """CUnetGeneratorv1 (networks/models.py:472-555): UnetGenerator whose conv0_1 also reads num_classes constant one-hot
+    planes of the image's label (:525-530).  The planes never exist here: conv0_1 stays the nf-channel launch over
+    W_f = weight[:, :nf], and the planes' share of its raw output -- which depends on the label, the output channel and
+    the border case of the pixel only -- is the `add_pre` operand of that launch (combat_cond_fwd).
+    Labels: slot buffer 'y', int32 [N] (`labels(slot)`), read by the launches when the plans run.
+
+    The parameter stays one [nf][nf + num_classes][3][3] tensor.  Its gradient has two producers: the nf-channel
+    weight-gradient launch writes W_f's part to the scratch `dwf01` (it addresses rows of c_real contiguous channels,
+    the parameter's rows hold nf + num_classes), and combat_cond_wgrad -- which has to run behind that launch on the same
+    gradient tensor anyway -- computes W_y's part and copies the scratch into the parameter's gradient rows: the merge
+    costs no launch of its own and no convolution kernel changes.  For the same reason W_f's packed operand is built
+    from `wf01`, a contiguous copy of weight[:, :nf] taken at every refresh()."""
+
+    def __init__(self, module):
+        self.num_classes = int(module.num_classes)
+        super().__init__(module)
+
+    def _w01(self) -> torch.Tensor:
+        """conv0_1.weight in the flat buffer: [nf][3][3][nf + num_classes]."""
+        return self.fp._slice(self.fp.flat, "conv0_1.weight").view(self.nf, 3, 3, self.nf + self.num_classes)
+
+    def _conv_operand(self, name: str, conv):
+        if name != "conv0_1":
+            return super()._conv_operand(name, conv)
+        nf = self.nf
+        self.wf01 = torch.empty(nf, 3, 3, nf, dtype=f32, device=self.device)
+        self.dwf01 = torch.zeros(nf, 9, nf, dtype=f32, device=self.device)
+        return self.wf01.permute(0, 3, 1, 2), nf
+
+    def refresh(self) -> None:
+        if self.weights_dirty:
+            self.wf01.copy_(self._w01()[..., :self.nf])
+        super().refresh()
+
+    def labels(self, slot: Slot) -> torch.Tensor:
+        """The labels the plans of `slot` condition on (int32 [N], zeros until written)."""
+        return slot.buf("y", (slot.N,), torch.int32, zero=True)
+
+    def _cond_forward(self, P: Plan, slot: Slot, s: int) -> dict:
+        y = self.labels(slot)
+        cond = slot.buf("cond", (slot.N, s, s, self.nf))
+        P.hold(y, cond)
+        P.add("cond", lib.combat_cond_fwd, self._w01().data_ptr() + 4 * self.nf, y.data_ptr(), slot.N, s, self.nf,
+              self.num_classes, cond.data_ptr())
+        return dict(add_pre=cond)
+
+    def _conv0_1_wgrad(self, P: Plan, slot: Slot, d) -> None:
+        nf = self.nf
+        # (the weight-gradient launch adds to a zeroed tensor; zeroed on the plan's stream, which the auxiliary queue follows)
+        P.add("conv0_1.dwf.zero", lib.combat_memset_zero, self.dwf01.data_ptr(), self.dwf01.numel() * 4)
+        rec_wgrad(P, "conv0_1.wgrad", slot.bufs["a.conv0_1"], d, self.pc["conv0_1"], self.dwf01)
+        if P.pending_reduces:        # (a deferred slab reduction: dwf01 must be final before it is copied)
+            P.flush_reduces()
+        taps = slot.buf("cond.taps", (slot.N, 9, nf), f32)
+        y = self.labels(slot)
+        dw = self.fp.grad_phys("conv0_1.weight")
+        P.hold(taps, y, dw, d)
+        # auxiliary like the bias column sums: consumed by the optimiser only
+        P.add("cond.wgrad", lib.combat_cond_wgrad, d.data_ptr(), y.data_ptr(), slot.N, d.shape[1], nf, self.num_classes,
+              self.dwf01.data_ptr(), dw.data_ptr(), taps.data_ptr(), aux=True, after=len(P.calls) - 1)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1905,8 +1981,8 @@ class FreqEngine(NetEngine):
 # drop-in module(x) with autograd (reference call signature; not the fast path)
 # --------------------------------------------------------------------------------------------
 
-ENGINES = {"preact_resnet18": PreActEngine, "resnet18": ResNetEngine, "unet": UnetEngine, "freq": FreqEngine,
-           "gridgen": GridEngine}
+ENGINES = {"preact_resnet18": PreActEngine, "resnet18": ResNetEngine, "unet": UnetEngine, "cunet": CUnetEngine,
+           "freq": FreqEngine, "gridgen": GridEngine}
 
 
 def build_engine(module) -> NetEngine:
@@ -1972,6 +2048,29 @@ class _GeneratorFn(torch.autograd.Function):
             "differentiate through combat_amd.step.AlternatedStep; module(x) is inference-only")
 
 
+class _CondGeneratorFn(torch.autograd.Function):
+    """noise = netG(x, y) of a CUnetGeneratorv1 (networks/models.py:523-555); inference-only like _GeneratorFn."""
+
+    @staticmethod
+    def forward(ctx, module, x, y, *params):
+        eng: CUnetEngine = module._net_engine()
+        eng.refresh()
+        n, _, hw, _ = x.shape
+        if n == 0:
+            return x.new_zeros(x.shape)
+        slot = eng.slot("module", pad_batch(n), hw)
+        _images_to_c8(x, eng.input(slot))
+        eng.labels(slot)[:n].copy_(y)
+        eng.forward_plan(slot).run()
+        out = torch.empty(slot.N, 3, hw, hw, dtype=f32, device=x.device)
+        ops.nhwc_to_nchw_f32(eng.output(slot), 3, out)
+        return out[:n]
+
+    @staticmethod
+    def backward(ctx, g):
+        raise NotImplementedError("module(x, y) is inference-only; the parameter gradients come from CUnetEngine.backward_plan")
+
+
 class _GridFn(torch.autograd.Function):
     """[B, 2, S, S] field of a GridGenerator: the same for every sample (see GridEngine).  Like the other modules'
     `module(x)` it is inference-only: a backward through it raises instead of handing the caller's own training
@@ -1990,6 +2089,26 @@ class _GridFn(torch.autograd.Function):
     def backward(ctx, g):
         raise NotImplementedError(
             "differentiate through combat_amd.step.WanetStep; module(x) is inference-only")
+
+
+def check_labels(y, n: int, num_classes: int) -> torch.Tensor:
+    """The labels of n images as F.one_hot takes them (networks/models.py:526): an integer tensor [n] with every entry
+    in 0..num_classes-1, else ValueError.  The range is checked on the host for a host tensor; for a device tensor it
+    is not read back (the kernels condition an out-of-range label on nothing)."""
+    y = torch.as_tensor(y)
+    if y.dim() != 1 or y.numel() != n or y.dtype.is_floating_point or y.dtype == torch.bool:
+        raise ValueError("labels must be an integer tensor [%d], got %s %s" % (n, y.dtype, tuple(y.shape)))
+    if y.device.type == "cpu" and n and (int(y.min()) < 0 or int(y.max()) >= num_classes):
+        raise ValueError("labels must lie in 0..%d, got %d..%d" % (num_classes - 1, int(y.min()), int(y.max())))
+    return y.to(torch.int32)
+
+
+def cond_module_forward(module, x: torch.Tensor, y) -> torch.Tensor:
+    """The reference's `netG(x, y)` (networks/models.py:523) on the HIP path."""
+    if x.device.type != "cuda":
+        raise CombatHipError("combat_amd modules run on the GPU only; got a %s tensor" % x.device)
+    y = check_labels(y, x.shape[0], module.num_classes)
+    return _CondGeneratorFn.apply(module, x, y, *tuple(module.parameters()))
 
 
 def module_forward(module, x: torch.Tensor) -> torch.Tensor:

@@ -8,6 +8,7 @@ which fails loudly when the gfx950 library is missing.
 
 Mirrored interfaces:
   UnetGenerator     networks/models.py:268-341
+  CUnetGeneratorv1  networks/models.py:472-555
   GridGenerator     networks/models.py:344-385
   PreActResNet18    classifier_models/preact_resnet.py:13-40, 72-110
   ResNet18          classifier_models/resnet.py:15-37, 68-106
@@ -77,6 +78,28 @@ class UnetGenerator(_HipModule):
             cin = in_channels if ci == 0 else nf * ci
             cout = out_channel if co == 0 else nf * co
             setattr(self, name, nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1, bias=use_bias))
+
+
+class CUnetGeneratorv1(_HipModule):
+    """The label-conditioned generator of the multi-label attack: UnetGenerator whose conv0_1 reads nf + num_classes
+    channels (networks/models.py:482).  `opt.num_classes` as in the reference; called as netG(x, y)."""
+
+    arch = "cunet"
+
+    def __init__(self, opt, in_channels=3, nf=64, use_bias=True, out_channel=None):
+        super().__init__()
+        self.num_classes = opt.num_classes
+        if out_channel is None:
+            out_channel = in_channels
+        self.in_channels, self.nf, self.out_channel = in_channels, nf, out_channel
+        for name, ci, co, stride, _ in UNET_LAYERS:
+            cin = in_channels if ci == 0 else nf * ci + (self.num_classes if name == "conv0_1" else 0)
+            cout = out_channel if co == 0 else nf * co
+            setattr(self, name, nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1, bias=use_bias))
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """float32 [N,3,H,W], integer labels [N] -> float32 noise [N,3,H,W]."""
+        return _engine().cond_module_forward(self, x, y)
 
 
 class GridGenerator(_HipModule):

@@ -322,6 +322,67 @@ def trigger_pair_bwd(x, noise, p_mat, k1, noise_rate, d_bd, out_bd, l2_scale, d_
           "combat_trigger_pair_bwd", str(tuple(x.shape)))
 
 
+def trigger_groups_fwd(x, noise, p_mat, k1, ps, noise_rate, out, mse_partial=None) -> None:
+    """trigger_fwd with k1 fp32 [ceil(n / ps)][3]: image i is blurred with k1[i // ps]."""
+    n, _, hw, _ = x.shape
+    if ps < 1 or k1.dtype != torch.float32 or k1.numel() < 3 * ((n + ps - 1) // max(ps, 1)) or not k1.is_contiguous():
+        raise ValueError("trigger_groups_fwd: k1 must be contiguous fp32 [ceil(%d / ps)][3] with ps >= 1, got ps = %d, %s %s"
+                         % (n, ps, k1.dtype, tuple(k1.shape)))
+    check(lib.combat_trigger_groups_fwd(x.data_ptr(), noise.data_ptr(), p_mat.data_ptr(), k1.data_ptr(), noise_rate, n, hw,
+                                        ps, out.data_ptr(), _p(mse_partial), _stream()),
+          "combat_trigger_groups_fwd", "%s ps=%d" % (tuple(x.shape), ps))
+
+
+def trigger_groups_bwd(x, noise, p_mat, k1, ps, noise_rate, d_out, out, l2_scale, d_noise, pre_tanh=False, d_out2=None) -> None:
+    """trigger_bwd with k1 fp32 [ceil(n / ps)][3]: image i is blurred with k1[i // ps]."""
+    n, _, hw, _ = x.shape
+    if ps < 1 or k1.dtype != torch.float32 or k1.numel() < 3 * ((n + ps - 1) // max(ps, 1)) or not k1.is_contiguous():
+        raise ValueError("trigger_groups_bwd: k1 must be contiguous fp32 [ceil(%d / ps)][3] with ps >= 1, got ps = %d, %s %s"
+                         % (n, ps, k1.dtype, tuple(k1.shape)))
+    check(lib.combat_trigger_groups_bwd(x.data_ptr(), noise.data_ptr(), p_mat.data_ptr(), k1.data_ptr(), noise_rate, n, hw,
+                                        ps, _p(d_out), _p(d_out2), _p(out), l2_scale, int(pre_tanh), d_noise.data_ptr(),
+                                        _stream()),
+          "combat_trigger_groups_bwd", "%s ps=%d" % (tuple(x.shape), ps))
+
+
+def _cond_shapes(what, w, labels, nf, classes, n):
+    """Everything the C side cannot see of a conditioning launch: w is conv0_1's weight as the flat parameter buffer
+    keeps it, fp32 [nf][9][nf + classes] contiguous; labels int32 [>= n]."""
+    if w.dtype != torch.float32 or tuple(w.shape) != (nf, 9, nf + classes) or not w.is_contiguous():
+        raise ValueError("%s: the weight (or its gradient) must be contiguous fp32 [%d][9][%d], got %s %s"
+                         % (what, nf, nf + classes, w.dtype, tuple(w.shape)))
+    if labels.dtype != torch.int32 or labels.dim() != 1 or labels.numel() < n or not labels.is_contiguous():
+        raise ValueError("%s: labels must be int32 [>= %d], got %s %s" % (what, n, labels.dtype, tuple(labels.shape)))
+
+
+def cond_fwd(w, labels, classes, cond) -> None:
+    """cond (bf16 [n][s][s][nf]) = the share of conv0_1's raw output that the one-hot planes of labels contribute
+    (include/combat_hip.h, combat_cond_fwd); w fp32 [nf][9][nf + classes]."""
+    n, s, s2, nf = cond.shape
+    _cond_shapes("cond_fwd", w, labels, nf, classes, n)
+    if cond.dtype != bf16 or s != s2 or not cond.is_contiguous():
+        raise ValueError("cond_fwd: cond must be contiguous bf16 [n][s][s][nf], got %s %s" % (cond.dtype, tuple(cond.shape)))
+    check(lib.combat_cond_fwd(w.data_ptr() + 4 * nf, labels.data_ptr(), n, s, nf, classes, cond.data_ptr(), _stream()),
+          "combat_cond_fwd", "n=%d hw_map=%d nf=%d classes=%d" % (n, s, nf, classes))
+
+
+def cond_wgrad(d, labels, classes, dw, scratch, dwf=None) -> None:
+    """dw[:, :, nf:] (fp32 [nf][9][nf + classes]) = the gradient of W_y from d (bf16 [n][s][s][nf], the gradient w.r.t.
+    conv0_1's raw output); dw[:, :, :nf] = dwf (fp32 [nf][9][nf]) if given (include/combat_hip.h, combat_cond_wgrad).
+    scratch: fp32, at least n * 9 * nf elements."""
+    n, s, s2, nf = d.shape
+    _cond_shapes("cond_wgrad", dw, labels, nf, classes, n)
+    if d.dtype != bf16 or s != s2 or not d.is_contiguous():
+        raise ValueError("cond_wgrad: d must be contiguous bf16 [n][s][s][nf], got %s %s" % (d.dtype, tuple(d.shape)))
+    if scratch.dtype != torch.float32 or scratch.numel() < n * 9 * nf or not scratch.is_contiguous():
+        raise ValueError("cond_wgrad: scratch must be contiguous fp32 with at least %d elements" % (n * 9 * nf))
+    if dwf is not None and (dwf.dtype != torch.float32 or dwf.numel() != nf * 9 * nf or not dwf.is_contiguous()):
+        raise ValueError("cond_wgrad: dwf must be contiguous fp32 [%d][9][%d]" % (nf, nf))
+    check(lib.combat_cond_wgrad(d.data_ptr(), labels.data_ptr(), n, s, nf, classes, _p(dwf), dw.data_ptr(), scratch.data_ptr(),
+                                _stream()),
+          "combat_cond_wgrad", "n=%d hw_map=%d nf=%d classes=%d" % (n, s, nf, classes))
+
+
 def augment_fwd(x, n, hw, out_c8, params=None, index=None, out_f32=None) -> None:
     check(lib.combat_augment_fwd(x.data_ptr(), _p(index), _p(params), n, hw, out_c8.data_ptr(), _p(out_f32),
                                  _stream()), "combat_augment_fwd", "n=%d hw=%d" % (n, hw))

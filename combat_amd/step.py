@@ -359,6 +359,10 @@ class AlternatedStep(PerBatchSize):
     def _fill_table_extra(self, hs, rnd, targets_cpu, bd_targets_cpu) -> None:
         """Entries of the step table a subclass adds (staging set `hs`, before its copy)."""
 
+    def _bd_targets(self, targets_cpu: torch.Tensor) -> torch.Tensor:
+        """The labels the poisoned images of Phase C are trained towards (train_generator.py:70-77, :181)."""
+        return create_targets_bd(targets_cpu, self.opt).cpu()
+
     def _gen_slot(self, n):
         return self.eG.slot("G", n, self.hw)
 
@@ -401,7 +405,7 @@ class AlternatedStep(PerBatchSize):
         s = self._setup(n)
         hw, st = self.hw, torch.cuda.current_stream().cuda_stream
         targets_cpu = targets_cpu.cpu()
-        bd_targets_cpu = create_targets_bd(targets_cpu, opt).cpu()
+        bd_targets_cpu = self._bd_targets(targets_cpu)
         if rnd is None:
             rnd = self._draw(targets_cpu, bd_targets_cpu)
         nb = rnd.num_bd
@@ -864,6 +868,139 @@ class InputAwareStep(AlternatedStep):
             for k in ("loss1", "correct1"):
                 if k in s.sC_eval.bufs:
                     s.sC_eval.bufs[k].zero_()
+
+
+LAB_Y = 7   # multi-label only: one int64 row read as int32 [2n] -- the generator's labels of Phase C, then of Phase G
+
+
+def chunk_size(bs: int, num_classes: int) -> int:
+    """ps of train_generator_multilabel.py:203: the generator phase cuts the batch into chunks of ps images."""
+    return (bs - 1) // num_classes + 1
+
+
+@dataclass
+class MultiLabelRandomness(StepRandomness):
+    """The draws of one multi-label step (train_generator_multilabel.py:171-236): StepRandomness with one blur sigma per
+    chunk of the generator phase (sigma_chunks[ci], :217) in place of sigma_g, which is unused."""
+
+    sigma_chunks: List[float] = field(default_factory=list)
+
+
+class MultiLabelStep(AlternatedStep):
+    """The alternated step of the multi-target-label attack (reference train_generator_multilabel.py:160-262) around the
+    label-conditioned generator (nets.CUnetGeneratorv1, engine.CUnetEngine).
+
+    Phase C (:164-190): num_bd = sum(rand(bs) < pc) over the whole batch, the poisoned images are the FIRST num_bd of
+    the batch in order, the generator is conditioned on their own labels and the targets stay as they are.
+    Phase G (:192-242): the batch is cut into chunks of ps = (bs - 1) // num_classes + 1 images; chunk ci is conditioned
+    on class ci and blurred with its own draw of the module-level GaussianBlur (:53; FIXED_BLUR); the loop ends with the
+    batch (bs = 16 on CIFAR-10: classes 0..7).  loss = CE(netC(bd), chunk classes) + L2_weight * MSE(bd, inputs)
+    + clean_model_weight * CE(clean(bd), targets) (:240; the gradient-L2 term of train_generator.py is absent).  bd_correct
+    and the clean model's ASR are scored against the chunk classes, its Bd BA against the clean labels (:226, :250-251).
+
+    Unlike AlternatedStep the two phases condition the generator differently, so it runs twice: an n-image forward
+    over the targets (slot 'G.c', only when num_bd > 0; the reference runs it on the num_bd images alone) and the
+    n-image forward + backward over the chunk classes (slot 'G').  Both read the same input buffer.  Labels travel in
+    the step table (row LAB_Y as int32 [2n]); the per-chunk blur kernels are rows 1.. of its blur section, consumed by
+    ONE combat_trigger_groups_fwd / _bwd launch.  Single rank only."""
+
+    FIXED_BLUR = True
+    CAN_MERGE_C = False
+
+    def __init__(self, netC, netG, clean_model, netF, opt, process_group=None):
+        if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
+            raise ValueError("MultiLabelStep runs on one rank only: data parallelism is not implemented for the "
+                             "multi-label attack (got a process group of %d ranks)"
+                             % torch.distributed.get_world_size(process_group))
+        if getattr(netG, "arch", "") != "cunet":
+            raise ValueError("MultiLabelStep needs the label-conditioned generator (nets.CUnetGeneratorv1), got %s"
+                             % type(netG).__name__)
+        if int(netG.num_classes) != int(opt.num_classes):
+            raise ValueError("MultiLabelStep: the generator conditions on %d classes, opt.num_classes is %d"
+                             % (netG.num_classes, opt.num_classes))
+        # augmentation tables, blur kernels (sigma_c + one per chunk, at most num_classes), label rows (+ LAB_Y)
+        self.TABLE = (5, 1 + int(opt.num_classes), 8)
+        super().__init__(netC, netG, clean_model, netF, opt, None)
+
+    def run(self, inputs: torch.Tensor, targets_cpu: torch.Tensor, rnd: Optional[MultiLabelRandomness] = None,
+            lr_c: Optional[float] = None, lr_g: Optional[float] = None, prof: Optional[list] = None) -> None:
+        """lr_g defaults to the reference's generator rate lr_C * 0.1 (:115)."""
+        if lr_g is None:
+            lr_g = float(self.opt.lr_C) * 0.1
+        super().run(inputs, targets_cpu, rnd, lr_c, lr_g, prof)
+
+    # ---- table, slots, plans
+    def _bd_targets(self, targets_cpu: torch.Tensor) -> torch.Tensor:
+        """Phase C leaves the targets unchanged (:180): every image is 'of its target class', so the poisoned ones are
+        the first num_bd of the batch in order and total_targets == targets."""
+        return targets_cpu.clone()
+
+    def _fill_table_extra(self, hs, rnd, targets_cpu, bd_targets_cpu) -> None:
+        n = targets_cpu.shape[0]
+        ps = chunk_size(n, int(self.opt.num_classes))
+        groups = (n + ps - 1) // ps
+        if len(rnd.sigma_chunks) < groups:
+            raise ValueError("MultiLabelStep: %d chunks need %d blur sigmas, got %d" % (groups, groups, len(rnd.sigma_chunks)))
+        chunk = torch.arange(n, dtype=torch.int64) // ps          # (:214: tmp = targets[si:ei] * 0 + ci)
+        lab = hs["targets"]
+        lab[LAB_BD].copy_(chunk)                                   # netC's loss and bd_correct (:226-228)
+        lab[LAB_K2][1].copy_(chunk)                                # the clean model's ASR (:251)
+        y = lab[LAB_Y].view(torch.int32)
+        y[:n].copy_(targets_cpu)                                   # Phase C: the images' own labels (:173-176)
+        y[n:].copy_(chunk)                                         # Phase G
+        for ci in range(groups):
+            hs["k1"][1 + ci].copy_(torch.from_numpy(trigger.gaussian_kernel1d(rnd.sigma_chunks[ci], self.opt.kernel_size)))
+        self.cur.nb, self.cur.ps = rnd.num_bd, ps      # (read by this step's hooks below, from the set they run on)
+
+    def _gen_plans(self, s) -> dict:
+        eG, n = self.eG, s.n
+        y = s.d_targets[LAB_Y].view(torch.int32)
+        s.sG.bufs["y"] = y[n:]
+        s.sGc = eG.slot("G.c", n, self.hw)
+        s.sGc.bufs["y"] = y[:n]
+        s.sGc.bufs["x"] = eG.input(s.sG)                           # one image buffer for both passes
+        return dict(G_f=eG.forward_plan(s.sG), G_b=eG.backward_plan(s.sG), Gc_f=eG.forward_plan(s.sGc))
+
+    # ---- the step's pieces
+    def _draw(self, targets_cpu, bd_targets_cpu) -> MultiLabelRandomness:
+        """Reference order: num_bd (:171), sigma_c (:176, only if num_bd > 0), aug0 (:179), aug1 (:190), aug2 (:199:
+        pred_clean's transform comes first in Phase G), one sigma per chunk (:217), aug3 (:225), aug4 (:236)."""
+        n = targets_cpu.shape[0]
+        num_bd = int(np.sum(np.random.rand(n) < self.opt.pc))
+        sigma_c = trigger.sample_sigma(self.sigma_range) if num_bd else 0.5
+        aug0, aug1, aug2 = (self.transforms.sample(n) for _ in range(3))
+        ps = chunk_size(n, int(self.opt.num_classes))
+        sig = [trigger.sample_sigma(self.sigma_range) for _ in range((n + ps - 1) // ps)]
+        aug3, aug4 = self.transforms.sample(n), self.transforms.sample(n)
+        return MultiLabelRandomness(num_bd, sigma_c, sig[0], [aug0, aug1, aug2, aug3, aug4], sigma_chunks=sig)
+
+    def _gen_forward(self, x_ptr, n, st, prof) -> None:
+        s = self.cur
+        ops.check(lib.combat_image_to_c8(x_ptr, n, self.hw, self.eG.input(s.sG).data_ptr(), st), "c8 G")
+        if s.nb:
+            s.pl["Gc_f"].run(prof)      # conditioned on the targets: Phase C's poisoned images
+        s.pl["G_f"].run(prof)           # conditioned on the chunk classes: Phase G
+
+    def _trigger_c(self, x_ptr, nb, k1c, st) -> None:
+        s = self.cur
+        ops.check(lib.combat_trigger_fwd(x_ptr, self.eG.output(s.sGc).data_ptr(), self.P.data_ptr(), k1c, float(self.opt.noise_rate),
+                                         nb, self.hw, s.tab_i[0].data_ptr(), s.cat_src[s.n:].data_ptr(), None, None, st),
+                  "trigger C")
+
+    def _trigger_g(self, x_ptr, n, k1g, s2) -> None:
+        s = self.cur
+        ops.check(lib.combat_trigger_groups_fwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g,
+                                                float(self.opt.noise_rate), n, self.hw, s.ps, s.bd.data_ptr(),
+                                                s.mse.data_ptr(), s2), "trigger groups")
+
+    def _gen_backward(self, x_ptr, n, k1g, st, prof) -> None:
+        s, hw = self.cur, self.hw
+        l2_scale = float(self.opt.L2_weight) / float(n * 3 * hw * hw)          # :229, :240
+        ops.check(lib.combat_trigger_groups_bwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g,
+                                                float(self.opt.noise_rate), n, hw, s.ps, s.d_bd.data_ptr(),
+                                                s.d_bd2.data_ptr(), s.bd.data_ptr(), l2_scale, 1,
+                                                s.sG.buf("g.z", (n, hw, hw, 8)).data_ptr(), st), "trigger groups bwd")
+        self._backward_allreduce(s.pl["G_b"], self.eG, prof)
 
 
 class ImperceptibleStep(AlternatedStep):

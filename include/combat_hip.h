@@ -414,6 +414,61 @@ int combat_trigger_pair_bwd(const float *x, const void *noise, const float *P, c
                             const float *out_bd, float l2_scale, const float *d_cross /* NULL: zero */, int32_t pre_tanh,
                             void *d_noise, void *stream);
 
+/* Grouped trigger of the multi-label step (train_generator_multilabel.py:203-224: the batch is cut into chunks of ps
+ * images, chunk ci is poisoned towards class ci and gets its own draw of GaussianBlur(3, (0.1, 1))).  These are
+ * combat_trigger_fwd / combat_trigger_bwd (without src_index / out_c8) with k1 fp32 [ceil(n / ps)][3]: image i is blurred
+ * with k1[i / ps]; the last group may be short.  Per image the arithmetic of the single-kernel entry points, in the same
+ * order: out, mse_partial and d_noise are bit-identical to one call of them per chunk.  COMBAT_EINVAL as for
+ * combat_trigger_fwd / _bwd, and for ps < 1. */
+int combat_trigger_groups_fwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
+                              int32_t n, int32_t hw, int32_t ps, float *out, float *mse_partial, void *stream);
+int combat_trigger_groups_bwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
+                              int32_t n, int32_t hw, int32_t ps, const float *d_out,
+                              const float *d_out2 /* NULL, or added to d_out */, const float *out, float l2_scale,
+                              int32_t pre_tanh, void *d_noise, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Label conditioning of the multi-label generator (CUnetGeneratorv1, networks/models.py:472-555).  The reference
+ * concatenates num_classes constant one-hot planes to conv0_0's output (:525-530), so conv0_1 reads nf + num_classes
+ * channels (:482).  The planes are constant over space and LeakyReLU leaves 0 and 1 unchanged; with
+ * W_f = conv0_1.weight[:, :nf] and W_y = conv0_1.weight[:, nf:] the raw output of conv0_1 is
+ *   conv(lrelu(f0), W_f)[n][y][x][o] + cond[n][y][x][o]
+ *   cond[n][y][x][o] = sum over the taps (r, s) with 0 <= y + r - 1 < hw_map and 0 <= x + s - 1 < hw_map of
+ *                      W_y[o][labels[n]][r][s]
+ * The convolution stays a 64-channel launch over W_f's packed operand; cond is its add_pre operand (added before the
+ * statistics of the launch's epilogue).  The weight is addressed in the layout the flat parameter buffer keeps it in,
+ * [nf][9][nf + num_classes] fp32 (output channel, tap = 3 r + s, input channel): W_y points at input channel nf of it,
+ * element (o, tap, c) is W_y[(o * 9 + tap) * (nf + num_classes) + c].  A pixel lies in one of nine regions
+ * k = 3 yr + xr, yr = 0 (y == 0), 1 (0 < y < hw_map - 1), 2 (y == hw_map - 1), xr alike; tap (r, s) is inside the map
+ * on the regions with (r, yr) and (s, xr) other than (0, 0) and (2, 2).
+ *
+ * combat_cond_fwd: cond_out bf16 [n][hw_map][hw_map][nf] = bf16 of the fp32 sum, from 0.0f, of the inside taps in
+ * ascending tap order: one rounding.  A label outside 0..num_classes-1 (F.one_hot raises) gives zeros.
+ *
+ * combat_cond_wgrad: d bf16 [n][hw_map][hw_map][nf] is the gradient with respect to conv0_1's raw output (the tensor
+ * handed to conv0_1's weight-gradient launch).  dW_y[o][c][tap] = sum over the images with labels[n] == c and the pixels
+ * where the tap is inside the map of d[n][p][o]; labels are data, nothing flows back to them.  fp32, no atomics, this
+ * fixed order (the same bits every run, in every mode):
+ *   region sums: with G = nf / 8 and L = 256 / G, lane l = 0..L-1 adds the pixels p = l, l + L, l + 2L, ... < hw_map^2
+ *                in order from 0.0f (a pixel outside the region adds +0.0f); the L lane sums are added in lane order
+ *                from 0.0f
+ *   tap sums:    the sums of the tap's regions, added in ascending region order starting from the first of them
+ *                -> scratch fp32 [n][9][nf]
+ *   class sums:  the tap sums of the class's images, added in ascending image order from 0.0f; a class no image carries
+ *                gets exactly 0
+ * dw fp32 [nf][9][nf + num_classes] is the parameter's gradient in the flat buffer's layout: the class sums are written
+ * (not added) to its input channels nf.., and if dwf != NULL (fp32 [nf][9][nf], the gradient the 64-channel
+ * weight-gradient launch left in a scratch of the caller) it is copied to input channels 0..nf-1: the merge of the two
+ * parts happens here, in the launch that has to follow the weight gradient anyway.
+ * COMBAT_EINVAL for hw_map < 2 (at 1 the first row is the last) or > 1024, nf outside {8, 16, 32, 64, 128, 256},
+ * num_classes outside 1..1024, n < 0, a NULL pointer other than dwf, cond_out / d not 16-byte or another pointer not
+ * 4-byte aligned; n == 0 launches nothing.
+ * ------------------------------------------------------------------------------------------ */
+int combat_cond_fwd(const float *W_y, const int32_t *labels, int32_t n, int32_t hw_map, int32_t nf, int32_t num_classes,
+                    void *cond_out, void *stream);
+int combat_cond_wgrad(const void *d, const int32_t *labels, int32_t n, int32_t hw_map, int32_t nf, int32_t num_classes,
+                      const float *dwf, float *dw, float *scratch, void *stream);
+
 /* Trigger of the imperceptible step (train_generator_imperceptible.py:67-75 create_inputs_bd, :228 loss_tv =
  * kornia.losses.total_variation(inputs_bd).mean(), :234-237 the loss line).  Per image, TV(out) = sum over C, H, W of
  * |out[y+1][x] - out[y][x]| + |out[y][x+1] - out[y][x]| (kornia 0.6.6; restated, not pinned against kornia itself).
