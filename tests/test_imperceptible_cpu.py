@@ -132,13 +132,17 @@ def _func(path, func):
     return next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == func)
 
 
-def test_log_keys_are_the_references():
-    fn = _func("train_generator_imperceptible.py", "train")
-    dicts = [n.args[1] for n in ast.walk(fn) if isinstance(n, ast.Call) and getattr(n.func, "attr", "") == "add_scalars"]
-    assert len(dicts) == 1 and {k.value for k in dicts[0].keys} == LOG_KEYS
-    src = ast.get_source_segment(open(os.path.join(ROOT, "train_generator_imperceptible.py")).read(), fn)
-    assert '"TV Loss": m["loss_tv_sum"] / ts' in src
-    assert "TV Loss" not in src.split("progress_bar(")[1].split("if last")[0]     # :266-277: the main script's line
+def test_log_keys_are_the_references(monkeypatch, capsys):
+    """:293-308: the epoch's scalars are train_generator.py's plus "TV Loss" = the epoch's TV sum over its samples;
+    :266-277: the progress line is the main script's, without a TV column."""
+    from test_entry_scripts_cpu import METRICS, _run_train
+    st, writer, _, lines, _, _ = _run_train("train_generator_imperceptible", monkeypatch, capsys)
+    ((tag, items, _),) = writer.scalars
+    assert tag == "Clean Accuracy" and {k for k, _ in items} == LOG_KEYS and len(items) == len(LOG_KEYS)
+    assert dict(items)["TV Loss"] == METRICS["loss_tv_sum"] / st.samples
+    _, _, _, base_lines, _, _ = _run_train("train_generator", monkeypatch, capsys)
+    assert [c[0] for c in lines[-1]] == [c[0] for c in base_lines[-1]] and len(lines[-1]) == 6
+    assert not any("TV" in label for line in lines for label, _ in line)
 
 
 def test_checkpoint_keys_and_eval_are_the_main_scripts():
@@ -151,18 +155,21 @@ def test_checkpoint_keys_and_eval_are_the_main_scripts():
     assert {k.value for k in saved.keys} == GEN_KEYS
 
 
-def test_resume_keeps_the_loaded_clean_model():
+def test_resume_keeps_the_loaded_clean_model(tmp_path, monkeypatch):
     """:518-534 restore netC / netG / optimisers / schedulers and not clean_model; train_generator.py restores it."""
-    fn = _func("train_generator_imperceptible.py", "main")
-    call = next(n for n in ast.walk(fn) if isinstance(n, ast.Call) and getattr(n.func, "attr", "") == "main")
-    kw = {k.arg: k.value for k in call.keywords}
-    assert isinstance(kw["resume_clean_model"], ast.Constant) and kw["resume_clean_model"].value is False
-    assert kw["prepare"].id == "fix_blur"
-    import inspect
-    import train_generator as base
-    assert inspect.signature(base.main).parameters["resume_clean_model"].default is True
-    src = inspect.getsource(base.main)
-    assert 'if resume_clean_model:\n            clean_model.load_state_dict(sd["clean_model"])' in src
+    from test_entry_scripts_cpu import Run, _resume_checkpoint, _same
+    seen = {}
+    for script in ("train_generator_imperceptible", "train_generator"):
+        (tmp_path / script).mkdir()
+        run = Run(script, tmp_path / script, monkeypatch, "--n_iters", "3", "--continue_training", "--allow_missing_F",
+                  "--kernel_size", "5")
+        sd = _resume_checkpoint(run, 2)
+        run.main()
+        (call,) = run.train_calls
+        assert _same(call["args"][0], sd["netC"]) and _same(call["args"][3], sd["netG"])
+        seen[script] = (call["clean_model_is_clean"], _same(call["args"][7], sd["clean_model"]), call["opt"].kernel_size)
+    assert seen["train_generator_imperceptible"] == (True, False, 3)       # --load_checkpoint_clean's copy; the fixed blur
+    assert seen["train_generator"] == (False, True, 5)
 
 
 def test_victim_script_delegates_to_train_victim():

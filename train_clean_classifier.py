@@ -2,15 +2,13 @@
 (reference train_clean_classifier.py:75-121 loop, :153-160 checkpoint keys, :191-193 path
 <checkpoints>/<saving_prefix>/<dataset>/<dataset>_<saving_prefix>.pth.tar)."""
 import os
-import time
 
 import torch
 
-import config
-from combat_amd import api, dist as cdist
+from combat_amd import api, dist as cdist, run
 from combat_amd.data import get_dataloader
-from combat_amd.log import SummaryWriter, progress_bar
-from combat_amd.nets import configure_dataset, default_classifier
+from combat_amd.log import progress_bar
+from combat_amd.nets import default_classifier
 from combat_amd.step import ClassifierStep
 
 
@@ -70,46 +68,14 @@ def eval(netC, optimizerC, schedulerC, test_dl, best_clean_acc, tf_writer, epoch
 
 
 def main():
-    opt = config.get_arguments().parse_args()
-    configure_dataset(opt)
-    rank, local_rank, world = cdist.init()
-    if opt.device == "cuda":
-        opt.device = "cuda:%d" % local_rank
-    if opt.seed is not None:
-        torch.manual_seed(opt.seed)
+    opt, rank, world = run.start(lambda seed, rank: torch.manual_seed(seed))     # torch only, as before any data parallelism
     train_dl = get_dataloader(opt, True, rank=rank, world=world)
     test_dl = get_dataloader(opt, False, shuffle=False, rank=rank, world=world)
-    netC, optimizerC, schedulerC = get_model(opt)
-    mode = opt.saving_prefix
-    opt.ckpt_folder = os.path.join(opt.checkpoints, mode, opt.dataset)
-    opt.ckpt_path = os.path.join(opt.ckpt_folder, "{}_{}.pth.tar".format(opt.dataset, mode))
-    opt.log_dir = os.path.join(opt.ckpt_folder, "log_dir")
-    best, epoch_current = 0.0, 0
-    if opt.continue_training and os.path.exists(opt.ckpt_path):
-        sd = torch.load(opt.ckpt_path, map_location=opt.device, weights_only=True)
-        netC.load_state_dict(sd["netC"])
-        optimizerC.load_state_dict(sd["optimizerC"])
-        schedulerC.load_state_dict(sd["schedulerC"])
-        api.load_momentum_from_optimizer(optimizerC, netC)
-        best, epoch_current = sd["best_clean_acc"], sd["epoch_current"]
-    else:
-        cdist.fresh_start(opt.ckpt_folder, rank)
-    if world > 1:
-        cdist.broadcast_module(netC)
-    if rank == 0:
-        os.makedirs(opt.log_dir, exist_ok=True)
-        tf_writer = SummaryWriter(log_dir=opt.log_dir)
-    else:
-        tf_writer = cdist.NullWriter()
-    train_dl.epoch = epoch_current      # a seeded, resumed run continues the sequence of epoch permutations
-    for epoch in range(epoch_current, opt.n_iters):
-        print("Epoch {}:".format(epoch + 1))
-        t0 = time.perf_counter()
-        train(netC, optimizerC, schedulerC, train_dl, tf_writer, epoch, opt)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        best = eval(netC, optimizerC, schedulerC, test_dl, best, tf_writer, epoch, opt)
-        print(" train {:.2f} s, eval + checkpoint {:.2f} s".format(t1 - t0, time.perf_counter() - t1))
+    models = netC, optimizerC, schedulerC = get_model(opt)
+    run.checkpoint_layout(opt, opt.saving_prefix)
+    best, epoch_current = run.resume_classifier(opt, rank, netC, optimizerC, schedulerC, ("best_clean_acc",))
+    run.broadcast(world, netC)
+    run.epoch_loop(opt, train, eval, models, (train_dl,), (test_dl,), (), best, epoch_current, run.writer(opt, rank))
 
 
 if __name__ == "__main__":

@@ -5,24 +5,32 @@ Drop-in for the reference script of the same name: same flags (config.py), same
 (reference train_generator.py:80-128, 131-318, 321-465, 468-609) -- the per-batch loop body
 (:170-290) runs as ``combat_amd.step.AlternatedStep`` on the HIP kernels.  CIFAR-10 + the default
 default classifier of the dataset (PreActResNet18 for cifar10, ResNet18 for celeba) / UNet / "original" detector;
-other --model / --dataset values raise.
+other --model / --dataset values raise.  ``main()`` and ``train()`` are composed from ``combat_amd.run``, the frame
+every training script shares; what is this script's own is its tables, ``get_model`` and ``eval``.
 
 Data parallel: ``python -m torch.distributed.run --nproc-per-node N train_generator.py ...`` gives
 every rank a disjoint shard of each epoch and averages the gradients over RCCL (combat_amd.dist).
 """
 import os
-import random
-import time
 
-import numpy as np
 import torch
 
-import config
-from combat_amd import api, dist as cdist
+from combat_amd import api, dist as cdist, run
 from combat_amd.data import get_dataloader
-from combat_amd.log import SummaryWriter, image_grid, progress_bar
-from combat_amd.nets import FrequencyModel, UnetGenerator, configure_dataset, default_classifier
+from combat_amd.log import progress_bar
+from combat_amd.nets import FrequencyModel, UnetGenerator, default_classifier
 from combat_amd.step import AlternatedStep, WanetStep, create_targets_bd  # noqa: F401  (re-exported like the reference)
+
+# the progress line's columns and the epoch's "Clean Accuracy" scalars (:264-277, :293-308), as (label, metric key)
+PROGRESS = (("Clean Acc", "clean_correct"), ("Bd Acc", "bd_correct"), ("F Acc", "f_correct"),
+            ("Clean Model Acc", "clean_model_correct"), ("Clean Model Bd BA", "clean_model_bd_ba"),
+            ("Clean Model Bd ASR", "clean_model_bd_asr"))
+ACCURACIES = (("Clean", "clean_correct"), ("Bd", "bd_correct"), ("F", "f_correct"), ("CleanModel Acc", "clean_model_correct"),
+              ("CleanModel Bd BA", "clean_model_bd_ba"), ("CleanModel Bd ASR", "clean_model_bd_asr"))
+SCALARS = ACCURACIES + (("L2 Loss", "loss_l2_sum"), ("Grad L2 Loss", "loss_grad_l2_sum"),
+                        ("CleanModel Loss", "clean_model_loss_sum"))
+BEST_KEYS = ("best_clean_acc", "best_bd_acc", "best_F_acc", "best_clean_model_acc", "best_clean_model_bd_ba",
+             "best_clean_model_bd_asr")
 
 
 def create_dir(path_dir):
@@ -43,55 +51,11 @@ def get_model(opt):
     return netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model
 
 
-def _step_of(netC, netG, clean_model, netF, opt) -> AlternatedStep:
-    st = netC.__dict__.get("_alt_step")
-    if st is None:
-        pg = torch.distributed.group.WORLD if torch.distributed.is_initialized() else None
-        cls = WanetStep if getattr(netG, "arch", "") == "gridgen" else AlternatedStep
-        st = cls(netC, netG, clean_model, netF, opt, process_group=pg)
-        netC.__dict__["_alt_step"] = st
-    return st
-
-
 def train(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, train_dl, tf_writer, epoch, opt):
-    print(" Train:")
-    netC.train()
-    netG.train()
-    clean_model.eval()
-    st = _step_of(netC, netG, clean_model, netF, opt)
-    st.reset_metrics()
-    n_batches = len(train_dl)
-    every = max(1, int(getattr(opt, "log_interval", 20)))
-    m = None
-    for batch_idx, (inputs, targets) in enumerate(train_dl):
-        st.run(inputs.to(opt.device, non_blocking=True), targets,
-               lr_c=optimizerC.param_groups[0]["lr"], lr_g=optimizerG.param_groups[0]["lr"])
-        last = batch_idx == n_batches - 1 or (opt.max_steps and batch_idx + 1 >= opt.max_steps)
-        if batch_idx % every == 0 or last:   # the reference formats device tensors every step (one sync each)
-            m = st.read_metrics()
-            ts = m["samples"]
-            progress_bar(
-                batch_idx, n_batches,
-                "Clean Acc: {:.4f} | Bd Acc: {:.4f} | F Acc: {:.4f} | Clean Model Acc: {:.4f} | Clean Model Bd BA: {:.4f} "
-                "| Clean Model Bd ASR: {:.4f}".format(
-                    m["clean_correct"] * 100.0 / ts, m["bd_correct"] * 100.0 / ts, m["f_correct"] * 100.0 / ts,
-                    m["clean_model_correct"] * 100.0 / ts, m["clean_model_bd_ba"] * 100.0 / ts,
-                    m["clean_model_bd_asr"] * 100.0 / ts))
-        if last:
-            break
-    ts = m["samples"]
-    if not epoch % 1:
-        tf_writer.add_scalars("Clean Accuracy", {
-            "Clean": m["clean_correct"] * 100.0 / ts, "Bd": m["bd_correct"] * 100.0 / ts, "F": m["f_correct"] * 100.0 / ts,
-            "CleanModel Acc": m["clean_model_correct"] * 100.0 / ts,
-            "CleanModel Bd BA": m["clean_model_bd_ba"] * 100.0 / ts,
-            "CleanModel Bd ASR": m["clean_model_bd_asr"] * 100.0 / ts,
-            "L2 Loss": m["loss_l2_sum"] / ts, "Grad L2 Loss": m["loss_grad_l2_sum"] / ts,
-            "CleanModel Loss": m["clean_model_loss_sum"] / ts}, epoch)
-    if not epoch % 20 and not isinstance(tf_writer, cdist.NullWriter):    # :310-315: the last batch and its backdoored copy (Phase G's inputs_bd) as an image grid
-        tf_writer.add_image("Images", image_grid(st.inputs, st.bd, opt), global_step=epoch)
-    schedulerC.step()
-    schedulerG.step()
+    step_cls = WanetStep if getattr(netG, "arch", "") == "gridgen" else AlternatedStep
+    run.alternated_epoch("train_generator.py", step_cls,
+                         (netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model), (train_dl,),
+                         PROGRESS, SCALARS, 20, tf_writer, epoch, opt)     # :310-315: the image grid every 20th epoch
 
 
 def eval(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, test_dl, best_clean_acc, best_bd_acc,
@@ -170,17 +134,6 @@ def eval(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean
             best_clean_model_bd_asr)
 
 
-def detector_checkpoint_path(opt):
-    """The reference looks under <F_checkpoints>/<dataset>/<F_model>/ (:504-507) while its shipped
-    files sit one level up as <dataset>_original_detector.pth.tar: probe both."""
-    folder = os.path.join(opt.F_checkpoints, opt.dataset)
-    name = "{}_{}_detector.pth.tar".format(opt.dataset, opt.F_model)
-    for p in (os.path.join(folder, opt.F_model, name), os.path.join(folder, name)):
-        if os.path.exists(p):
-            return p
-    return os.path.join(folder, opt.F_model, name)
-
-
 def main(get_model=None, train=None, eval=None, prepare=None, resume_clean_model=True):
     """``get_model`` / ``train`` / ``eval`` default to this module's; train_generator_wanet.py passes its own.
     ``prepare(opt)`` runs on the parsed options before anything reads them; ``resume_clean_model=False`` keeps the
@@ -189,88 +142,16 @@ def main(get_model=None, train=None, eval=None, prepare=None, resume_clean_model
     get_model = get_model or globals()["get_model"]
     train = train or globals()["train"]
     eval = eval or globals()["eval"]
-    opt = config.get_arguments().parse_args()
-    configure_dataset(opt)
-    if prepare is not None:
-        prepare(opt)
-    rank, local_rank, world = cdist.init()
-    if opt.device == "cuda":
-        opt.device = "cuda:%d" % local_rank
-    if opt.seed is not None:
-        torch.manual_seed(opt.seed)
-        np.random.seed(opt.seed + rank)
-        random.seed(opt.seed + rank)
-
+    opt, rank, world = run.start(run.seed_ranks_apart, prepare)
     train_dl = get_dataloader(opt, True, rank=rank, world=world)
     test_dl = get_dataloader(opt, False, shuffle=False, rank=rank, world=world)
-    netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model = get_model(opt)
-
-    mode = opt.saving_prefix
-    opt.ckpt_folder = os.path.join(opt.checkpoints, "{}_clean".format(mode), opt.dataset)
-    opt.ckpt_path = os.path.join(opt.ckpt_folder, "{}_{}_clean.pth.tar".format(opt.dataset, mode))
-    opt.log_dir = os.path.join(opt.ckpt_folder, "log_dir")
-
-    opt.F_ckpt_path = detector_checkpoint_path(opt)
-    print(f"Loading {opt.F_model} at {opt.F_ckpt_path}")
-    if os.path.exists(opt.F_ckpt_path):
-        netF.load_state_dict(torch.load(opt.F_ckpt_path, map_location=opt.device, weights_only=True)["netC"])
-    elif not opt.allow_missing_F:
-        print("Error: {} not found (pass --allow_missing_F to run with an untrained detector)".format(opt.F_ckpt_path))
-        exit()
-    netF.eval()
-    print("Done")
-
-    load_path = os.path.join(opt.checkpoints, opt.load_checkpoint_clean or "", opt.dataset,
-                             "{}_{}.pth.tar".format(opt.dataset, opt.load_checkpoint_clean))
-    if not os.path.exists(load_path):
-        print("Error: {} not found".format(load_path))
-        exit()
-    clean_model.load_state_dict(torch.load(load_path, map_location=opt.device, weights_only=True)["netC"])
-    clean_model.eval()
-
-    if opt.continue_training:
-        if not os.path.exists(opt.ckpt_path):
-            print("Pretrained model doesnt exist")
-            exit()
-        print("Continue training!!")
-        sd = torch.load(opt.ckpt_path, map_location=opt.device, weights_only=True)
-        netC.load_state_dict(sd["netC"])
-        optimizerC.load_state_dict(sd["optimizerC"])
-        schedulerC.load_state_dict(sd["schedulerC"])
-        netG.load_state_dict(sd["netG"])
-        optimizerG.load_state_dict(sd["optimizerG"])
-        schedulerG.load_state_dict(sd["schedulerG"])
-        if resume_clean_model:
-            clean_model.load_state_dict(sd["clean_model"])
-        api.load_momentum_from_optimizer(optimizerC, netC)
-        api.load_momentum_from_optimizer(optimizerG, netG)
-        best = [sd[k] for k in ("best_clean_acc", "best_bd_acc", "best_F_acc", "best_clean_model_acc",
-                                "best_clean_model_bd_ba", "best_clean_model_bd_asr")]
-        epoch_current = sd["epoch_current"]
-    else:
-        print("Train from scratch!!!")
-        best = [0.0] * 6
-        epoch_current = 0
-        cdist.fresh_start(opt.ckpt_folder, rank)   # the reference wipes the folder too (:562); rank 0 only, then a barrier
-    if world > 1:
-        for m in (netC, netG, clean_model, netF):
-            cdist.broadcast_module(m)
-    if rank == 0:    # one writer, one checkpoint file: rank 0's (every rank holds the same replicas)
-        create_dir(opt.log_dir)
-        tf_writer = SummaryWriter(log_dir=opt.log_dir)
-    else:
-        tf_writer = cdist.NullWriter()
-
-    train_dl.epoch = epoch_current      # a seeded, resumed run continues the sequence of epoch permutations
-    for epoch in range(epoch_current, opt.n_iters):
-        print("Epoch {}:".format(epoch + 1))
-        t0 = time.perf_counter()
-        train(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, train_dl, tf_writer, epoch, opt)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        best = list(eval(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, test_dl, *best,
-                         tf_writer, epoch, opt))
-        print(" train {:.2f} s, eval + checkpoint {:.2f} s".format(t1 - t0, time.perf_counter() - t1))
+    models = netC, _, _, netG, _, _, netF, clean_model = get_model(opt)
+    run.checkpoint_layout(opt, "{}_clean".format(opt.saving_prefix))
+    run.load_detector(netF, opt)
+    run.load_clean_model(clean_model, opt)
+    best, epoch_current, _ = run.resume_or_start(opt, rank, models, BEST_KEYS, restore_clean_model=resume_clean_model)
+    run.broadcast(world, netC, netG, clean_model, netF)
+    run.epoch_loop(opt, train, eval, models, (train_dl,), (test_dl,), (), best, epoch_current, run.writer(opt, rank))
 
 
 if __name__ == "__main__":

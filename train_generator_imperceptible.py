@@ -18,21 +18,14 @@ The per-batch body (:160-277) runs as ``combat_amd.step.ImperceptibleStep`` on t
 Data parallel: ``python -m torch.distributed.run --nproc-per-node N ...`` as train_generator.py.  That path has not
 been run on more than one GPU with this step.
 """
-import torch
-
 import train_generator as base
-from combat_amd import dist as cdist
-from combat_amd.log import image_grid, progress_bar
+from combat_amd import run
 from combat_amd.step import ImperceptibleStep, create_targets_bd  # noqa: F401  (re-exported like the reference)
 
 create_dir = base.create_dir
 eval = base.eval      # :313-440: train_generator.py's, with create_inputs_bd's fixed blur (fix_blur)
-
-
-def fix_blur(opt):
-    """gauss_smooth = T.GaussianBlur(kernel_size=3, sigma=(0.1, 1)) (:52), whatever the flags say."""
-    opt.kernel_size = 3
-    opt.sigma = (0.1, 1.0)
+fix_blur = run.fix_blur
+SCALARS = base.SCALARS[:-1] + (("TV Loss", "loss_tv_sum"),) + base.SCALARS[-1:]      # :293-308
 
 
 def get_model(opt):
@@ -41,54 +34,10 @@ def get_model(opt):
     return base.get_model(opt)
 
 
-def _step_of(netC, netG, clean_model, netF, opt) -> ImperceptibleStep:
-    st = netC.__dict__.get("_tv_step")
-    if st is None:
-        pg = torch.distributed.group.WORLD if torch.distributed.is_initialized() else None
-        st = ImperceptibleStep(netC, netG, clean_model, netF, opt, process_group=pg)
-        netC.__dict__["_tv_step"] = st
-    return st
-
-
 def train(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, train_dl, tf_writer, epoch, opt):
-    print(" Train:")
-    netC.train()
-    netG.train()
-    clean_model.eval()
-    st = _step_of(netC, netG, clean_model, netF, opt)
-    st.reset_metrics()
-    n_batches = len(train_dl)
-    every = max(1, int(getattr(opt, "log_interval", 20)))
-    m = None
-    for batch_idx, (inputs, targets) in enumerate(train_dl):
-        st.run(inputs.to(opt.device, non_blocking=True), targets,
-               lr_c=optimizerC.param_groups[0]["lr"], lr_g=optimizerG.param_groups[0]["lr"])
-        last = batch_idx == n_batches - 1 or (opt.max_steps and batch_idx + 1 >= opt.max_steps)
-        if batch_idx % every == 0 or last:
-            m = st.read_metrics()
-            ts = m["samples"]
-            progress_bar(
-                batch_idx, n_batches,
-                "Clean Acc: {:.4f} | Bd Acc: {:.4f} | F Acc: {:.4f} | Clean Model Acc: {:.4f} | Clean Model Bd BA: {:.4f} "
-                "| Clean Model Bd ASR: {:.4f}".format(
-                    m["clean_correct"] * 100.0 / ts, m["bd_correct"] * 100.0 / ts, m["f_correct"] * 100.0 / ts,
-                    m["clean_model_correct"] * 100.0 / ts, m["clean_model_bd_ba"] * 100.0 / ts,
-                    m["clean_model_bd_asr"] * 100.0 / ts))
-        if last:
-            break
-    ts = m["samples"]
-    if not epoch % 1:
-        tf_writer.add_scalars("Clean Accuracy", {
-            "Clean": m["clean_correct"] * 100.0 / ts, "Bd": m["bd_correct"] * 100.0 / ts, "F": m["f_correct"] * 100.0 / ts,
-            "CleanModel Acc": m["clean_model_correct"] * 100.0 / ts,
-            "CleanModel Bd BA": m["clean_model_bd_ba"] * 100.0 / ts,
-            "CleanModel Bd ASR": m["clean_model_bd_asr"] * 100.0 / ts,
-            "L2 Loss": m["loss_l2_sum"] / ts, "Grad L2 Loss": m["loss_grad_l2_sum"] / ts,
-            "TV Loss": m["loss_tv_sum"] / ts, "CleanModel Loss": m["clean_model_loss_sum"] / ts}, epoch)
-        if not isinstance(tf_writer, cdist.NullWriter):     # :306: the last batch and its backdoored copy
-            tf_writer.add_image("Images", image_grid(st.inputs, st.bd, opt), global_step=epoch)
-    schedulerC.step()
-    schedulerG.step()
+    run.alternated_epoch("train_generator_imperceptible.py", ImperceptibleStep,
+                         (netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model), (train_dl,),
+                         base.PROGRESS, SCALARS, 1, tf_writer, epoch, opt)      # :306: the image grid every epoch
 
 
 def main():

@@ -20,28 +20,23 @@ Data parallel: ``python -m torch.distributed.run --nproc-per-node N ...`` shards
 not run over RCCL on several GPUs.
 """
 import os
-import random
-import time
 
-import numpy as np
 import torch
 
-import config
 import train_generator as base
-from combat_amd import api, dist as cdist
+from combat_amd import api, dist as cdist, run
 from combat_amd.data import get_dataloader
-from combat_amd.log import SummaryWriter, image_grid, progress_bar
-from combat_amd.nets import configure_dataset
+from combat_amd.log import progress_bar
 from combat_amd.step import InputAwareStep, create_targets_bd  # noqa: F401  (re-exported like the reference)
 
 create_dir = base.create_dir
+fix_blur = run.fix_blur
+_rows_like = run.rows_like
 SECOND_LOADER_SEED = 104729    # offset of the second train loader's permutation seed when --seed is given
-
-
-def fix_blur(opt):
-    """gauss_smooth = T.GaussianBlur(kernel_size=3, sigma=(0.1, 1)) (:53), whatever the flags say."""
-    opt.kernel_size = 3
-    opt.sigma = (0.1, 1.0)
+PROGRESS = base.PROGRESS[:3] + (("Cross Acc", "cross_correct"),) + base.PROGRESS[3:]       # :293-304
+SCALARS = (base.ACCURACIES[:2] + (("Cross", "cross_correct"),) + base.ACCURACIES[2:]       # :310-326
+           + (("L2 Loss", "loss_l2_sum"), ("CleanModel Loss", "clean_model_loss_sum")))
+BEST_KEYS = base.BEST_KEYS[:2] + ("best_cross_acc",) + base.BEST_KEYS[2:]
 
 
 def get_model(opt):
@@ -51,65 +46,11 @@ def get_model(opt):
     return netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model
 
 
-def _step_of(netC, netG, clean_model, netF, opt) -> InputAwareStep:
-    st = netC.__dict__.get("_ia_step")
-    if st is None:
-        pg = torch.distributed.group.WORLD if torch.distributed.is_initialized() else None
-        st = InputAwareStep(netC, netG, clean_model, netF, opt, process_group=pg)
-        netC.__dict__["_ia_step"] = st
-    return st
-
-
-def _rows_like(x2, n):
-    """The second loader's batch cut (or wrapped) to n rows: under data parallel a shuffled loader pads its shard
-    while the evaluation loader keeps exact shards, so the last batches may differ in size."""
-    if x2.shape[0] == n:
-        return x2
-    reps = (n + x2.shape[0] - 1) // x2.shape[0]
-    return torch.cat([x2] * reps)[:n]
-
-
 def train(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, train_dl, train_dl2, mask,
           pattern, tf_writer, epoch, opt):
-    print(" Train:")
-    netC.train()
-    netG.train()
-    clean_model.eval()
-    st = _step_of(netC, netG, clean_model, netF, opt)
-    st.reset_metrics()
-    n_batches = len(train_dl)
-    every = max(1, int(getattr(opt, "log_interval", 20)))
-    m = None
-    for batch_idx, (inputs, targets), (inputs2, _) in zip(range(n_batches), train_dl, train_dl2):
-        inputs2 = _rows_like(inputs2, inputs.shape[0])
-        st.run(inputs.to(opt.device, non_blocking=True), targets, inputs2.to(opt.device, non_blocking=True),
-               lr_c=optimizerC.param_groups[0]["lr"], lr_g=optimizerG.param_groups[0]["lr"])
-        last = batch_idx == n_batches - 1 or (opt.max_steps and batch_idx + 1 >= opt.max_steps)
-        if batch_idx % every == 0 or last:
-            m = st.read_metrics()
-            ts = m["samples"]
-            progress_bar(
-                batch_idx, n_batches,
-                "Clean Acc: {:.4f} | Bd Acc: {:.4f} | F Acc: {:.4f} | Cross Acc: {:.4f} | Clean Model Acc: {:.4f} | "
-                "Clean Model Bd BA: {:.4f} | Clean Model Bd ASR: {:.4f}".format(
-                    m["clean_correct"] * 100.0 / ts, m["bd_correct"] * 100.0 / ts, m["f_correct"] * 100.0 / ts,
-                    m["cross_correct"] * 100.0 / ts, m["clean_model_correct"] * 100.0 / ts,
-                    m["clean_model_bd_ba"] * 100.0 / ts, m["clean_model_bd_asr"] * 100.0 / ts))
-        if last:
-            break
-    ts = m["samples"]
-    if not epoch % 1:
-        tf_writer.add_scalars("Clean Accuracy", {
-            "Clean": m["clean_correct"] * 100.0 / ts, "Bd": m["bd_correct"] * 100.0 / ts,
-            "Cross": m["cross_correct"] * 100.0 / ts, "F": m["f_correct"] * 100.0 / ts,
-            "CleanModel Acc": m["clean_model_correct"] * 100.0 / ts,
-            "CleanModel Bd BA": m["clean_model_bd_ba"] * 100.0 / ts,
-            "CleanModel Bd ASR": m["clean_model_bd_asr"] * 100.0 / ts,
-            "L2 Loss": m["loss_l2_sum"] / ts, "CleanModel Loss": m["clean_model_loss_sum"] / ts}, epoch)
-        if not isinstance(tf_writer, cdist.NullWriter):     # :310-331: the last batch and its backdoored copy
-            tf_writer.add_image("Images", image_grid(st.inputs, st.bd, opt), global_step=epoch)
-    schedulerC.step()
-    schedulerG.step()
+    run.alternated_epoch("train_generator_inputaware.py", InputAwareStep,
+                         (netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model),
+                         (train_dl, train_dl2), PROGRESS, SCALARS, 1, tf_writer, epoch, opt)     # :310-331: the grid every epoch
 
 
 def eval(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, test_dl, test_dl2, mask, pattern,
@@ -193,22 +134,8 @@ def _accuracies(c):
                 cm_asr=c["cm_asr"] * 100.0 / bd_n)
 
 
-BEST_KEYS = ("best_clean_acc", "best_bd_acc", "best_cross_acc", "best_F_acc", "best_clean_model_acc",
-             "best_clean_model_bd_ba", "best_clean_model_bd_asr")
-
-
 def main():
-    opt = config.get_arguments().parse_args()
-    configure_dataset(opt)
-    fix_blur(opt)
-    rank, local_rank, world = cdist.init()
-    if opt.device == "cuda":
-        opt.device = "cuda:%d" % local_rank
-    if opt.seed is not None:
-        torch.manual_seed(opt.seed)
-        np.random.seed(opt.seed + rank)
-        random.seed(opt.seed + rank)
-
+    opt, rank, world = run.start(run.seed_ranks_apart, fix_blur)
     train_dl = get_dataloader(opt, True, rank=rank, world=world)
     test_dl = get_dataloader(opt, False, shuffle=False, rank=rank, world=world)
     train_dl2 = get_dataloader(opt, True, rank=rank, world=world)
@@ -216,77 +143,14 @@ def main():
     if opt.seed is not None:     # a seeded loader derives its permutations from --seed: keep the two train orders apart
         train_dl2.base_seed += SECOND_LOADER_SEED
         test_dl2.base_seed += SECOND_LOADER_SEED
-    netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model = get_model(opt)
-
-    mode = opt.saving_prefix
-    opt.ckpt_folder = os.path.join(opt.checkpoints, "{}_clean".format(mode), opt.dataset)
-    opt.ckpt_path = os.path.join(opt.ckpt_folder, "{}_{}_clean.pth.tar".format(opt.dataset, mode))
-    opt.log_dir = os.path.join(opt.ckpt_folder, "log_dir")
-
-    opt.F_ckpt_path = base.detector_checkpoint_path(opt)
-    print(f"Loading {opt.F_model} at {opt.F_ckpt_path}")
-    if os.path.exists(opt.F_ckpt_path):
-        netF.load_state_dict(torch.load(opt.F_ckpt_path, map_location=opt.device, weights_only=True)["netC"])
-    elif not opt.allow_missing_F:
-        print("Error: {} not found (pass --allow_missing_F to run with an untrained detector)".format(opt.F_ckpt_path))
-        exit()
-    netF.eval()
-    print("Done")
-
-    load_path = os.path.join(opt.checkpoints, opt.load_checkpoint_clean or "", opt.dataset,
-                             "{}_{}.pth.tar".format(opt.dataset, opt.load_checkpoint_clean))
-    if not os.path.exists(load_path):
-        print("Error: {} not found".format(load_path))
-        exit()
-    clean_model.load_state_dict(torch.load(load_path, map_location=opt.device, weights_only=True)["netC"])
-    clean_model.eval()
-
-    if opt.continue_training:
-        if not os.path.exists(opt.ckpt_path):
-            print("Pretrained model doesnt exist")
-            exit()
-        print("Continue training!!")
-        sd = torch.load(opt.ckpt_path, map_location=opt.device, weights_only=True)
-        netC.load_state_dict(sd["netC"])
-        optimizerC.load_state_dict(sd["optimizerC"])
-        schedulerC.load_state_dict(sd["schedulerC"])
-        netG.load_state_dict(sd["netG"])
-        optimizerG.load_state_dict(sd["optimizerG"])
-        schedulerG.load_state_dict(sd["schedulerG"])
-        clean_model.load_state_dict(sd["clean_model"])
-        api.load_momentum_from_optimizer(optimizerC, netC)
-        api.load_momentum_from_optimizer(optimizerG, netG)
-        best = [sd[k] for k in BEST_KEYS]
-        epoch_current = sd["epoch_current"]
-        mask, pattern = sd["mask"].to(opt.device), sd["pattern"].to(opt.device)
-    else:
-        print("Train from scratch!!!")
-        best = [0.0] * len(BEST_KEYS)
-        epoch_current = 0
-        mask = torch.zeros(opt.input_height, opt.input_width, device=opt.device)     # :621-623 (saved, never used)
-        mask[2:6, 2:6] = 0.1
-        pattern = torch.rand(opt.input_channel, opt.input_height, opt.input_width).to(opt.device)
-        cdist.fresh_start(opt.ckpt_folder, rank)
-    if world > 1:
-        for m in (netC, netG, clean_model, netF):
-            cdist.broadcast_module(m)
-    if rank == 0:
-        create_dir(opt.log_dir)
-        tf_writer = SummaryWriter(log_dir=opt.log_dir)
-    else:
-        tf_writer = cdist.NullWriter()
-
-    train_dl.epoch = train_dl2.epoch = epoch_current
-    for epoch in range(epoch_current, opt.n_iters):
-        print("Epoch {}:".format(epoch + 1))
-        t0 = time.perf_counter()
-        train(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, train_dl, train_dl2, mask,
-              pattern, tf_writer, epoch, opt)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        best = list(eval(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, test_dl, test_dl2,
-                         mask, pattern, *best, tf_writer, epoch, opt))
-        print(" train {:.2f} s, eval + checkpoint {:.2f} s".format(t1 - t0, time.perf_counter() - t1))
+    models = netC, _, _, netG, _, _, netF, clean_model = get_model(opt)
+    run.checkpoint_layout(opt, "{}_clean".format(opt.saving_prefix))
+    run.load_detector(netF, opt)
+    run.load_clean_model(clean_model, opt)
+    best, epoch_current, mask_pattern = run.resume_or_start(opt, rank, models, BEST_KEYS, mask_pattern=True)   # :597-623
+    run.broadcast(world, netC, netG, clean_model, netF)
+    run.epoch_loop(opt, train, eval, models, (train_dl, train_dl2), (test_dl, test_dl2), mask_pattern, best, epoch_current,
+                   run.writer(opt, rank))
 
 
 if __name__ == "__main__":

@@ -20,28 +20,19 @@ The reference's F-model table (:19-28) names detectors this repository has no en
 
 Single process only: MultiLabelStep has no data-parallel path and refuses a process group of more than one rank.
 """
-import os
-import random
-import time
-
-import numpy as np
 import torch
 
-import config
 import train_generator as base
-from combat_amd import api, dist as cdist
+from combat_amd import api, run
 from combat_amd.data import get_dataloader
-from combat_amd.log import SummaryWriter, image_grid, progress_bar
-from combat_amd.nets import CUnetGeneratorv1, FrequencyModel, configure_dataset, default_classifier
+from combat_amd.log import progress_bar
+from combat_amd.nets import CUnetGeneratorv1, FrequencyModel, default_classifier
 from combat_amd.step import MultiLabelStep, create_targets_bd  # noqa: F401  (re-exported like the reference)
 
 create_dir = base.create_dir
-
-
-def fix_blur(opt):
-    """gauss_smooth = T.GaussianBlur(kernel_size=3, sigma=(0.1, 1)) (:53), whatever the flags say."""
-    opt.kernel_size = 3
-    opt.sigma = (0.1, 1.0)
+fix_blur = run.fix_blur
+BEST_KEYS = base.BEST_KEYS
+SCALARS = base.ACCURACIES + (("L2 Loss", "loss_l2_sum"), ("CleanModel Loss", "clean_model_loss_sum"))     # :288-302
 
 
 def create_inputs_bd(inputs, targets, netG, opt):
@@ -68,55 +59,11 @@ def get_model(opt):
     return netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model
 
 
-def _step_of(netC, netG, clean_model, netF, opt) -> MultiLabelStep:
-    st = netC.__dict__.get("_ml_step")
-    if st is None:
-        pg = torch.distributed.group.WORLD if torch.distributed.is_initialized() else None
-        st = MultiLabelStep(netC, netG, clean_model, netF, opt, process_group=pg)
-        netC.__dict__["_ml_step"] = st
-    return st
-
-
 def train(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, train_dl, mask, pattern, tf_writer,
           epoch, opt):
-    print(" Train:")
-    netC.train()
-    netG.train()
-    clean_model.eval()
-    st = _step_of(netC, netG, clean_model, netF, opt)
-    st.reset_metrics()
-    n_batches = len(train_dl)
-    every = max(1, int(getattr(opt, "log_interval", 20)))
-    m = None
-    for batch_idx, (inputs, targets) in enumerate(train_dl):
-        st.run(inputs.to(opt.device, non_blocking=True), targets,
-               lr_c=optimizerC.param_groups[0]["lr"], lr_g=optimizerG.param_groups[0]["lr"])
-        last = batch_idx == n_batches - 1 or (opt.max_steps and batch_idx + 1 >= opt.max_steps)
-        if batch_idx % every == 0 or last:
-            m = st.read_metrics()
-            ts = m["samples"]
-            progress_bar(
-                batch_idx, n_batches,
-                "Clean Acc: {:.4f} | Bd Acc: {:.4f} | F Acc: {:.4f} | Clean Model Acc: {:.4f} | Clean Model Bd BA: {:.4f} | "
-                "Clean Model Bd ASR: {:.4f}".format(
-                    m["clean_correct"] * 100.0 / ts, m["bd_correct"] * 100.0 / ts, m["f_correct"] * 100.0 / ts,
-                    m["clean_model_correct"] * 100.0 / ts, m["clean_model_bd_ba"] * 100.0 / ts,
-                    m["clean_model_bd_asr"] * 100.0 / ts))
-        if last:
-            break
-    if m is None:
-        raise SystemExit("train_generator_multilabel.py: the train loader yielded no batch (dataset smaller than one batch?)")
-    ts = m["samples"]
-    if not epoch % 1:
-        tf_writer.add_scalars("Clean Accuracy", {
-            "Clean": m["clean_correct"] * 100.0 / ts, "Bd": m["bd_correct"] * 100.0 / ts, "F": m["f_correct"] * 100.0 / ts,
-            "CleanModel Acc": m["clean_model_correct"] * 100.0 / ts,
-            "CleanModel Bd BA": m["clean_model_bd_ba"] * 100.0 / ts,
-            "CleanModel Bd ASR": m["clean_model_bd_asr"] * 100.0 / ts,
-            "L2 Loss": m["loss_l2_sum"] / ts, "CleanModel Loss": m["clean_model_loss_sum"] / ts}, epoch)
-        tf_writer.add_image("Images", image_grid(st.inputs, st.bd, opt), global_step=epoch)
-    schedulerC.step()
-    schedulerG.step()
+    run.alternated_epoch("train_generator_multilabel.py", MultiLabelStep,
+                         (netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model), (train_dl,),
+                         base.PROGRESS, SCALARS, 1, tf_writer, epoch, opt)
 
 
 def _accuracies(c, num_classes):
@@ -185,91 +132,18 @@ def eval(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean
             best_clean_model_bd_asr)
 
 
-BEST_KEYS = ("best_clean_acc", "best_bd_acc", "best_F_acc", "best_clean_model_acc", "best_clean_model_bd_ba",
-             "best_clean_model_bd_asr")
-
-
 def main():
-    opt = config.get_arguments().parse_args()
-    configure_dataset(opt)
-    fix_blur(opt)
-    rank, local_rank, world = cdist.init()
-    if world > 1:
-        raise SystemExit("train_generator_multilabel.py runs as one process: the multi-label step has no data-parallel path")
-    if opt.device == "cuda":
-        opt.device = "cuda:%d" % local_rank
-    if opt.seed is not None:
-        torch.manual_seed(opt.seed)
-        np.random.seed(opt.seed)
-        random.seed(opt.seed)
-
+    opt, rank, world = run.start(run.seed_ranks_apart, fix_blur, one_process="train_generator_multilabel.py runs as one "
+                                 "process: the multi-label step has no data-parallel path")
     train_dl = get_dataloader(opt, True)
     test_dl = get_dataloader(opt, False, shuffle=False)
-    netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model = get_model(opt)
-
-    mode = opt.saving_prefix
-    opt.ckpt_folder = os.path.join(opt.checkpoints, "{}_clean".format(mode), opt.dataset)
-    opt.ckpt_path = os.path.join(opt.ckpt_folder, "{}_{}_clean.pth.tar".format(opt.dataset, mode))
-    opt.log_dir = os.path.join(opt.ckpt_folder, "log_dir")
-
-    opt.F_ckpt_path = base.detector_checkpoint_path(opt)
-    print(f"Loading {opt.F_model} at {opt.F_ckpt_path}")
-    if os.path.exists(opt.F_ckpt_path):
-        netF.load_state_dict(torch.load(opt.F_ckpt_path, map_location=opt.device, weights_only=True)["netC"])
-    elif not opt.allow_missing_F:
-        print("Error: {} not found (pass --allow_missing_F to run with an untrained detector)".format(opt.F_ckpt_path))
-        exit()
-    netF.eval()
-    print("Done")
-
-    load_path = os.path.join(opt.checkpoints, opt.load_checkpoint_clean or "", opt.dataset,
-                             "{}_{}.pth.tar".format(opt.dataset, opt.load_checkpoint_clean))
-    if not os.path.exists(load_path):
-        print("Error: {} not found".format(load_path))
-        exit()
-    clean_model.load_state_dict(torch.load(load_path, map_location=opt.device, weights_only=True)["netC"])
-    clean_model.eval()
-
-    if opt.continue_training:
-        if not os.path.exists(opt.ckpt_path):
-            print("Pretrained model doesnt exist")
-            exit()
-        print("Continue training!!")
-        sd = torch.load(opt.ckpt_path, map_location=opt.device, weights_only=True)
-        netC.load_state_dict(sd["netC"])
-        optimizerC.load_state_dict(sd["optimizerC"])
-        schedulerC.load_state_dict(sd["schedulerC"])
-        netG.load_state_dict(sd["netG"])
-        optimizerG.load_state_dict(sd["optimizerG"])
-        schedulerG.load_state_dict(sd["schedulerG"])
-        clean_model.load_state_dict(sd["clean_model"])
-        api.load_momentum_from_optimizer(optimizerC, netC)
-        api.load_momentum_from_optimizer(optimizerG, netG)
-        best = [sd[k] for k in BEST_KEYS]
-        epoch_current = sd["epoch_current"]
-        mask, pattern = sd["mask"].to(opt.device), sd["pattern"].to(opt.device)
-    else:
-        print("Train from scratch!!!")
-        best = [0.0] * len(BEST_KEYS)
-        epoch_current = 0
-        mask = torch.zeros(opt.input_height, opt.input_width, device=opt.device)     # :557-560 (saved, never used)
-        mask[2:6, 2:6] = 0.1
-        pattern = torch.rand(opt.input_channel, opt.input_height, opt.input_width).to(opt.device)
-        cdist.fresh_start(opt.ckpt_folder, rank)
-    create_dir(opt.log_dir)
-    tf_writer = SummaryWriter(log_dir=opt.log_dir)
-
-    train_dl.epoch = epoch_current
-    for epoch in range(epoch_current, opt.n_iters):
-        print("Epoch {}:".format(epoch + 1))
-        t0 = time.perf_counter()
-        train(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, train_dl, mask, pattern,
-              tf_writer, epoch, opt)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        best = list(eval(netC, optimizerC, schedulerC, netG, optimizerG, schedulerG, netF, clean_model, test_dl, mask, pattern,
-                         *best, tf_writer, epoch, opt))
-        print(" train {:.2f} s, eval + checkpoint {:.2f} s".format(t1 - t0, time.perf_counter() - t1))
+    models = _, _, _, _, _, _, netF, clean_model = get_model(opt)
+    run.checkpoint_layout(opt, "{}_clean".format(opt.saving_prefix))
+    run.load_detector(netF, opt)
+    run.load_clean_model(clean_model, opt)
+    best, epoch_current, mask_pattern = run.resume_or_start(opt, rank, models, BEST_KEYS, mask_pattern=True)   # :557-560
+    run.epoch_loop(opt, train, eval, models, (train_dl,), (test_dl,), mask_pattern, best, epoch_current,
+                   run.writer(opt, rank))
 
 
 if __name__ == "__main__":

@@ -1,15 +1,13 @@
 """Victim training on data poisoned by the frozen generator (reference train_victim.py:93-165 loop,
 :168-231 eval, :221-229 checkpoint keys; dataset flags from utils/dataloader_cleanbd.py:131-158)."""
 import os
-import time
 
 import torch
 
-import config
-from combat_amd import api, dist as cdist
+from combat_amd import api, dist as cdist, run
 from combat_amd.data import get_dataloader
-from combat_amd.log import SummaryWriter, image_grid, progress_bar
-from combat_amd.nets import UnetGenerator, configure_dataset, default_classifier
+from combat_amd.log import image_grid, progress_bar
+from combat_amd.nets import UnetGenerator, default_classifier
 from combat_amd.step import ClassifierStep, create_targets_bd
 
 
@@ -102,65 +100,22 @@ def load_generator(netG, load_path, opt):
 
 
 def main(get_model=None, wanet=False, eval=None, clean_folder=None):
-    """``get_model`` / ``eval`` default to this module's: train_victim_wanet.py passes its own get_model,
-    train_victim_inputaware.py its own get_model and eval.  clean_folder (default: wanet): the checkpoint lives under
-    <saving_prefix>_clean/."""
+    """``get_model`` / ``eval`` default to this module's: train_victim_wanet.py passes its own get_model.  clean_folder
+    (default: wanet): the checkpoint lives under <saving_prefix>_clean/.  train_victim_inputaware.py, with its second
+    test loader and third best value, composes its own main() from the same pieces."""
     get_model = get_model or globals()["get_model"]
     eval = eval or globals()["eval"]
     clean_folder = wanet if clean_folder is None else clean_folder
-    opt = config.get_arguments().parse_args()
-    configure_dataset(opt)
-    rank, local_rank, world = cdist.init()
-    if opt.device == "cuda":
-        opt.device = "cuda:%d" % local_rank
-    if opt.seed is not None:
-        import random
-        import numpy as np
-        torch.manual_seed(opt.seed)
-        np.random.seed(opt.seed + rank)
-        random.seed(opt.seed)     # the poisoned index set must be the same on every rank (it is also broadcast)
+    opt, rank, world = run.start(run.seed_shared_poison)
     train_dl = get_dataloader(opt, True, poisoned=True, rank=rank, world=world)
     test_dl = get_dataloader(opt, False, shuffle=False, poisoned=True, rank=rank, world=world)
-    netC, optimizerC, schedulerC, netG = get_model(opt)
+    models = netC, optimizerC, schedulerC, netG = get_model(opt)
     # train_victim.py:255-257 saves under <prefix>/, train_victim_wanet.py:241-243 under <prefix>_clean/
-    mode = "{}_clean".format(opt.saving_prefix) if clean_folder else opt.saving_prefix
-    opt.ckpt_folder = os.path.join(opt.checkpoints, mode, opt.dataset)
-    opt.ckpt_path = os.path.join(opt.ckpt_folder, "{}_{}.pth.tar".format(opt.dataset, mode))
-    opt.log_dir = os.path.join(opt.ckpt_folder, "log_dir")
-    load_path = os.path.join(opt.checkpoints, opt.load_checkpoint, opt.dataset,
-                             "{}_{}.pth.tar".format(opt.dataset, opt.load_checkpoint))
-    if not os.path.exists(load_path):
-        print("Error: {} not found".format(load_path))
-        exit()
-    load_generator(netG, load_path, opt)
-    best_clean_acc = best_bd_acc = 0.0
-    epoch_current = 0
-    if opt.continue_training and os.path.exists(opt.ckpt_path):
-        sd = torch.load(opt.ckpt_path, map_location=opt.device, weights_only=True)
-        netC.load_state_dict(sd["netC"])
-        optimizerC.load_state_dict(sd["optimizerC"])
-        schedulerC.load_state_dict(sd["schedulerC"])
-        api.load_momentum_from_optimizer(optimizerC, netC)
-        best_clean_acc, best_bd_acc, epoch_current = sd["best_clean_acc"], sd["best_bd_acc"], sd["epoch_current"]
-    else:
-        cdist.fresh_start(opt.ckpt_folder, rank)
-    if world > 1:
-        cdist.broadcast_module(netC)
-    if rank == 0:
-        os.makedirs(opt.log_dir, exist_ok=True)
-        tf_writer = SummaryWriter(log_dir=opt.log_dir)
-    else:
-        tf_writer = cdist.NullWriter()
-    train_dl.epoch = epoch_current      # a seeded, resumed run continues the sequence of epoch permutations
-    for epoch in range(epoch_current, opt.n_iters):
-        print("Epoch {}:".format(epoch + 1))
-        t0 = time.perf_counter()
-        train(netC, optimizerC, schedulerC, netG, train_dl, tf_writer, epoch, opt)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        best_clean_acc, best_bd_acc = eval(netC, optimizerC, schedulerC, netG, test_dl, best_clean_acc, best_bd_acc,
-                                           tf_writer, epoch, opt)
-        print(" train {:.2f} s, eval + checkpoint {:.2f} s".format(t1 - t0, time.perf_counter() - t1))
+    run.checkpoint_layout(opt, "{}_clean".format(opt.saving_prefix) if clean_folder else opt.saving_prefix)
+    load_generator(netG, run.saved_checkpoint(opt, opt.load_checkpoint), opt)
+    best, epoch_current = run.resume_classifier(opt, rank, netC, optimizerC, schedulerC, ("best_clean_acc", "best_bd_acc"))
+    run.broadcast(world, netC)
+    run.epoch_loop(opt, train, eval, models, (train_dl,), (test_dl,), (), best, epoch_current, run.writer(opt, rank))
 
 
 if __name__ == "__main__":

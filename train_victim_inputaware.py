@@ -15,13 +15,13 @@ import os
 import torch
 
 import train_victim as base
-from combat_amd import api, dist as cdist
+from combat_amd import api, dist as cdist, run
 from combat_amd.data import get_dataloader
 from combat_amd.log import progress_bar
 from combat_amd.step import create_targets_bd
 from train_generator_inputaware import _rows_like, fix_blur
 
-_state = {}     # the second test loader and best_cross_acc, across the epochs of one run
+BEST_KEYS = ("best_clean_acc", "best_bd_acc", "best_cross_acc")
 
 
 def get_model(opt):
@@ -29,24 +29,11 @@ def get_model(opt):
     return base.get_model(opt)
 
 
-def _second_loader(opt):
-    if "test_dl2" not in _state:
-        rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
-        world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
-        _state["test_dl2"] = get_dataloader(opt, False, rank=rank, world=world)     # shuffled, as the reference's
-        best = 0.0
-        if opt.continue_training and os.path.exists(opt.ckpt_path):
-            best = torch.load(opt.ckpt_path, map_location="cpu", weights_only=True).get("best_cross_acc", 0.0)
-        _state["best_cross_acc"] = best
-    return _state["test_dl2"]
-
-
-def eval(netC, optimizerC, schedulerC, netG, test_dl, best_clean_acc, best_bd_acc, tf_writer, epoch, opt):
+def eval(netC, optimizerC, schedulerC, netG, test_dl, test_dl2, best_clean_acc, best_bd_acc, best_cross_acc, tf_writer, epoch,
+         opt):
     print(" Eval:")
     netC.eval()
     cdist.average_bn_buffers(netC)
-    test_dl2 = _second_loader(opt)
-    best_cross_acc = _state["best_cross_acc"]
     n = nb = correct = bd = cross = 0
     for batch_idx, batch, batch2 in zip(range(len(test_dl)), test_dl, test_dl2):
         inputs, targets = batch[0].to(opt.device), batch[1].to(opt.device)
@@ -73,17 +60,26 @@ def eval(netC, optimizerC, schedulerC, netG, test_dl, best_clean_acc, best_bd_ac
     if acc_clean > best_clean_acc:
         print(" Saving...")
         best_clean_acc, best_bd_acc, best_cross_acc = acc_clean, acc_bd, acc_cross
-        _state["best_cross_acc"] = best_cross_acc
         if int(os.environ.get("RANK", 0)) == 0:
             api.sync_momentum_to_optimizer(optimizerC, netC)
             torch.save({"netC": netC.state_dict(), "schedulerC": schedulerC.state_dict(),
                         "optimizerC": optimizerC.state_dict(), "netG": netG.state_dict(), "best_clean_acc": acc_clean,
                         "best_bd_acc": acc_bd, "best_cross_acc": acc_cross, "epoch_current": epoch}, opt.ckpt_path)
-    return best_clean_acc, best_bd_acc
+    return best_clean_acc, best_bd_acc, best_cross_acc
 
 
 def main():
-    base.main(get_model=get_model, eval=eval, clean_folder=True)
+    opt, rank, world = run.start(run.seed_shared_poison)
+    train_dl = get_dataloader(opt, True, poisoned=True, rank=rank, world=world)
+    test_dl = get_dataloader(opt, False, shuffle=False, poisoned=True, rank=rank, world=world)
+    test_dl2 = get_dataloader(opt, False, rank=rank, world=world)     # shuffled, as the reference's (:281-283)
+    models = netC, optimizerC, schedulerC, netG = get_model(opt)
+    run.checkpoint_layout(opt, "{}_clean".format(opt.saving_prefix))      # :289-291
+    base.load_generator(netG, run.saved_checkpoint(opt, opt.load_checkpoint), opt)
+    best, epoch_current = run.resume_classifier(opt, rank, netC, optimizerC, schedulerC, BEST_KEYS)
+    run.broadcast(world, netC)
+    run.epoch_loop(opt, base.train, eval, models, (train_dl,), (test_dl, test_dl2), (), best, epoch_current,
+                   run.writer(opt, rank))
 
 
 if __name__ == "__main__":
