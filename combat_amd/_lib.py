@@ -85,6 +85,8 @@ SIGNATURES = {
     "combat_conv_wgrad": (C.c_int, [C.POINTER(WgradArgs), c_vp]),
     "combat_conv_wgrad_workspace_bytes": (c_i64, [C.POINTER(WgradArgs)]),
     "combat_conv_wgrad_reduce": (C.c_int, [C.POINTER(WgradArgs), c_vp]),
+    "combat_conv_wgrad_group": (C.c_int, [C.POINTER(C.POINTER(WgradArgs)), c_i32, c_vp, c_i64, c_vp]),
+    "combat_conv_wgrad_group_workspace_bytes": (c_i64, [C.POINTER(C.POINTER(WgradArgs)), c_i32]),
     "combat_pack_weights": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32,
                                       c_i32, c_vp]),
     "combat_norm_finalize": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -26,6 +26,9 @@ int conv_wgrad3x3_try(const combat_wgrad_args *a, hipStream_t st);
 int conv_wgrad3x3_dma_try(const combat_wgrad_args *a, hipStream_t st);   // same, for inputs without a prologue
 long conv_wgrad3x3_dma_workspace(const combat_wgrad_args *a);             // scratch bytes it can use (0: not applicable)
 int conv_wgrad3x3_dma_reduce(const combat_wgrad_args *a, hipStream_t st);  // the reduction a defer_reduce launch left out
+// up to four same-geometry problems in one kernel launch + one reduction launch (combat_conv_wgrad_group)
+int conv_wgrad3x3_dma_group(const combat_wgrad_args *const *members, int n, void *workspace, long workspace_bytes, hipStream_t st);
+long conv_wgrad3x3_dma_group_workspace(const combat_wgrad_args *const *members, int n);   // bytes for the n slab regions; -1: no group
 
 template <int BM, int BN, int WGM_ = 0>
 struct TileCfg {

@@ -632,6 +632,23 @@ extern "C" int combat_conv_wgrad_reduce(const combat_wgrad_args *a, void *stream
     return conv_wgrad3x3_dma_reduce(a, as_stream(stream));
 }
 
+extern "C" int64_t combat_conv_wgrad_group_workspace_bytes(const combat_wgrad_args *const *members, int32_t n) {
+    if (!members || n < 1) return COMBAT_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (validate_wgrad_args(members[i]) != COMBAT_OK) return COMBAT_EINVAL;
+    const long bytes = conv_wgrad3x3_dma_group_workspace(members, n);
+    return bytes < 0 ? COMBAT_EINVAL : bytes;
+}
+
+extern "C" int combat_conv_wgrad_group(const combat_wgrad_args *const *members, int32_t n, void *workspace, int64_t workspace_bytes,
+                                       void *stream) {
+    COMBAT_PLAN_HOOK(combat_conv_wgrad_group, members, n, workspace, workspace_bytes);
+    if (!members || n < 1) return COMBAT_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (validate_wgrad_args(members[i]) != COMBAT_OK) return COMBAT_EINVAL;
+    return conv_wgrad3x3_dma_group(members, n, workspace, (long)workspace_bytes, as_stream(stream));
+}
+
 extern "C" int combat_conv_wgrad(const combat_wgrad_args *a, void *stream) {
     COMBAT_PLAN_HOOK(combat_conv_wgrad, a);
     if (validate_wgrad_args(a) != COMBAT_OK) return COMBAT_EINVAL;

@@ -160,8 +160,12 @@ __device__ __forceinline__ void reduce_slabs(const float *__restrict__ ws, float
 // sharing, not this loop, sets the pace.
 // RED: the launch first folds an earlier launch's slabs (reduce_first): its own instantiation, so that the default
 // kernels keep their scalar-register budget (with the fold compiled in they spilled nine SGPRs)
+// src_p / dy_p / dw_p / ws_p / bid: the problem's operands, gradient, slab base and the workgroup's index inside the problem
+// -- for a single launch the fields of `p` and blockIdx.x; for a grouped launch (conv_wgrad3x3_dma_group_kernel) the
+// member's, selected ONCE by the caller and passed by value
 template <int HPW, int NS, bool RED>
-__device__ __forceinline__ void wgrad3x3_dma_body(const W3dParams &p) {
+__device__ __forceinline__ void wgrad3x3_dma_body(const W3dParams &p, const void *src_p, const void *dy_p, float *dw_p, float *ws_p,
+                                                  const int bid_in) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const combat_wgrad_args &a = p.a;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -175,7 +179,7 @@ __device__ __forceinline__ void wgrad3x3_dma_body(const W3dParams &p) {
         reduce_slabs<512>(p.red_ws, p.red_dw, p.red_base, p.red_tiles_c, p.red_split, p.red_k_real, p.red_c_real, smem, blockIdx.x, gridDim.x);
         __syncthreads();       // (the scratch is the first DMA stage)
     }
-    int bid = blockIdx.x;
+    int bid = bid_in;
     const int tile_c = bid % p.tiles_c; bid /= p.tiles_c;
     const int tile_k = bid % p.tiles_k;
     const int sp = bid / p.tiles_k;
@@ -204,11 +208,11 @@ __device__ __forceinline__ void wgrad3x3_dma_body(const W3dParams &p) {
         w[3] = 0x00020000u;
         return w;
     };
-    const u32x4_t xrs = rsrc_words(a.src, p.x_bytes), dyrs = rsrc_words(a.dy, p.dy_bytes);
+    const u32x4_t xrs = rsrc_words(src_p, p.x_bytes), dyrs = rsrc_words(dy_p, p.dy_bytes);
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(lds_void_t *)smem) + wid * 1024;
 #ifdef COMBAT_WGRAD_BUILTIN_DMA
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.src), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t dyrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.dy), 0, p.dy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(src_p), 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t dyrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(dy_p), 0, p.dy_bytes, 0x00020000);
 #define COMBAT_W3_DMA(rs_builtin, rs_words, lds_off, voff) \
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_builtin, (lds_void_t *)(smem + (lds_off) + wid * 1024), 16, voff, 0, 0, 0)
 #else
@@ -444,8 +448,8 @@ __device__ __forceinline__ void wgrad3x3_dma_body(const W3dParams &p) {
     // [dy fragment i][wave][lane] x 4 floats, i.e. every accumulator register quad as one 16-byte store, 1 KB per
     // wave instruction, no LDS pass and no barrier (the row-major form cost 9 x (LDS image + two barriers) = 9.5 k of a
     // workgroup's 57 k cycles); wgrad3x3_reduce_kernel maps a quad back to its (row, column).
-    if (p.ws) {
-        float *slab = p.ws + (size_t)blockIdx.x * 9 * 4096;
+    if (ws_p) {
+        float *slab = ws_p + (size_t)bid_in * 9 * 4096;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
@@ -481,7 +485,7 @@ __device__ __forceinline__ void wgrad3x3_dma_body(const W3dParams &p) {
             for (int idx = tid; idx < 64 * 64; idx += 512) {
                 const int row = idx >> 6, col = idx & 63;
                 const int n = k0 + row, c = c0 + col;
-                if (n < a.k_real && c < a.c_real) atomicAdd(a.dw + ((size_t)n * 9 + tap) * a.c_real + c, ep[row * EPS + col]);
+                if (n < a.k_real && c < a.c_real) atomicAdd(dw_p + ((size_t)n * 9 + tap) * a.c_real + c, ep[row * EPS + col]);
             }
             __syncthreads();
         }
@@ -499,8 +503,8 @@ __device__ __forceinline__ void wgrad3x3_dma_body(const W3dParams &p) {
 // kernel's fragment order (256 threads each), grid.y: groups of ranges (each adds its share with one fp32 atomic
 // per element -- a few per element instead of `split`).  Quad f4 of a tap = [dy fragment i][wave][lane]:
 // rows (i * 2 + (wave & 1)) * 16 + (lane >> 4) * 4 + 0..3 of column (wave >> 1) * 16 + (lane & 15).
-__global__ __launch_bounds__(256) void wgrad3x3_reduce_kernel(const float *__restrict__ ws, float *__restrict__ dw,
-                                                              int base, int tiles_c, int split, int k_real, int c_real) {
+__device__ __forceinline__ void reduce_ranges(const float *__restrict__ ws, float *__restrict__ dw, int base, int tiles_c, int split,
+                                              int k_real, int c_real) {
     const long e4 = (long)blockIdx.x * 256 + threadIdx.x;          // quad index inside [base][9][1024]
     if (e4 >= (long)base * 9 * 1024) return;
     const int f4 = (int)(e4 & 1023), tap = (int)((e4 >> 10) % 9), tile = (int)(e4 / (9 * 1024));
@@ -533,6 +537,45 @@ __global__ __launch_bounds__(256) void wgrad3x3_reduce_kernel(const float *__res
     }
 }
 
+__global__ __launch_bounds__(256) void wgrad3x3_reduce_kernel(const float *__restrict__ ws, float *__restrict__ dw,
+                                                              int base, int tiles_c, int split, int k_real, int c_real) {
+    reduce_ranges(ws, dw, base, tiles_c, split, k_real, c_real);
+}
+
+// A grouped launch (conv_wgrad3x3_dma_group): up to four problems of ONE geometry computed by one kernel launch and
+// reduced by one reduction launch.  The member is a grid dimension of its own; a workgroup selects its member's
+// pointers once, by value, from constant positions of the argument block (a run-time index into the kernel arguments
+// inside a loop made the gather pair kernel reload them every step: DESIGN section 5).
+constexpr int kGroupMax = 4;
+struct W3dGroup {
+    const void *src[kGroupMax];
+    const void *dy[kGroupMax];
+    float *dw[kGroupMax];
+    float *ws[kGroupMax];
+};
+template <class T>
+__device__ __forceinline__ T pick_member(const T (&v)[kGroupMax], int m) {
+    T r = v[0];
+    if (m == 1) r = v[1];
+    if (m == 2) r = v[2];
+    if (m == 3) r = v[3];
+    return r;
+}
+
+// the two reduction forms over every member's slabs: blockIdx.z = member; per member the grid, and with it every
+// element's summation order, is that of the single launch
+__global__ __launch_bounds__(256) void wgrad3x3_reduce_group_kernel(const W3dGroup g, int base, int tiles_c, int split, int k_real,
+                                                                    int c_real) {
+    const int m = blockIdx.z;
+    reduce_ranges(pick_member(g.ws, m), pick_member(g.dw, m), base, tiles_c, split, k_real, c_real);
+}
+__global__ __launch_bounds__(256) void wgrad3x3_reduce_det_group_kernel(const W3dGroup g, int base, int tiles_c, int split, int k_real,
+                                                                        int c_real) {
+    __shared__ __attribute__((aligned(16))) unsigned char scratch[256 * 64];
+    const int m = blockIdx.y;
+    reduce_slabs<256>(pick_member(g.ws, m), pick_member(g.dw, m), base, tiles_c, split, k_real, c_real, scratch, blockIdx.x, gridDim.x);
+}
+
 // stand-alone form of reduce_slabs (the last weight gradient of a queue has no successor to ride with; launches
 // without defer_reduce): 256 workgroups of 256 threads
 __global__ __launch_bounds__(256) void wgrad3x3_reduce_det_kernel(const float *__restrict__ ws, float *__restrict__ dw, int base,
@@ -543,7 +586,18 @@ __global__ __launch_bounds__(256) void wgrad3x3_reduce_det_kernel(const float *_
 
 // (the body is a device function: the host pass cannot see the buffer-resource type it uses)
 template <int HPW, int NS, bool RED>
-__global__ __launch_bounds__(512, 1) void conv_wgrad3x3_dma_kernel(const W3dParams p) { wgrad3x3_dma_body<HPW, NS, RED>(p); }
+__global__ __launch_bounds__(512, 1) void conv_wgrad3x3_dma_kernel(const W3dParams p) {
+    wgrad3x3_dma_body<HPW, NS, RED>(p, p.a.src, p.a.dy, p.a.dw, p.ws, blockIdx.x);
+}
+
+// grouped form: grid (workgroups of one member, members).  Its own kernel, so that the single-problem instantiations
+// keep their register budget; the patch loop is the same body.
+template <int HPW, int NS>
+__global__ __launch_bounds__(512, 1) void conv_wgrad3x3_dma_group_kernel(const W3dParams p, const W3dGroup g) {
+    const int m = blockIdx.y;
+    wgrad3x3_dma_body<HPW, NS, false>(p, pick_member(g.src, m), pick_member(g.dy, m), pick_member(g.dw, m), pick_member(g.ws, m),
+                                      blockIdx.x);
+}
 
 template <int HPW, int NS, bool RED>
 int launch_w3d_red(const W3dParams &p, int blocks, hipStream_t st) {
@@ -558,6 +612,23 @@ int launch_w3d_red(const W3dParams &p, int blocks, hipStream_t st) {
         attr = true;
     }
     COMBAT_LAUNCH(kern, dim3(blocks), dim3(512), smem, st, p);
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+
+template <int HPW, int NS>
+int launch_w3d_group(const W3dParams &p, const W3dGroup &g, int blocks, int n, hipStream_t st) {
+    constexpr int stage = 8192 + HPW * 8192;
+    constexpr int ep = 64 * 68 * 4;
+    constexpr int smem = NS * stage > ep ? NS * stage : ep;
+    auto kern = conv_wgrad3x3_dma_group_kernel<HPW, NS>;
+    static bool attr = false;
+    if (!attr) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
+            return COMBAT_ELAUNCH;
+        attr = true;
+    }
+    COMBAT_LAUNCH(kern, dim3(blocks, n), dim3(512), smem, st, p, g);
     CB_LAUNCH_CHECK();
     return COMBAT_OK;
 }
@@ -641,26 +712,34 @@ bool w3d_plan(const combat_wgrad_args *a, W3dParams &p) {
     return true;
 }
 
+// Which reduction form a launch takes, in one place for the single and the grouped launch.
+// Default: the round-3 reduction (ranges dealt to <= 14 groups of workgroups, one fp32 atomic per element and group):
+// 4-8 us back to back.  COMBAT_WGRAD_DET_REDUCE=1: reduce_slabs() as a launch of its own -- fixed summation order, no
+// atomics, bit-reproducible -- 9-18 us (tools/wgrad_chain_bench.py): a workgroup owns whole elements, so the slabs
+// of an element cannot be spread over the chip.
+// deterministic mode: with >= 4 tiles (144 workgroups of 256 quads) ONE group of ranges fills enough of the chip
+// and owns its elements (`dw += sum`, ranges in ascending order, no atomics): the round-3 kernel as it is; the
+// 64-channel layers (one tile, up to 256 ranges) take reduce_slabs(), which spreads an element's slabs over lanes
+bool reduce_by_ranges(int base) {
+    static const bool env_det = getenv("COMBAT_WGRAD_DET_REDUCE") != nullptr;
+    return !env_det && (!combat_deterministic() || base >= 4);
+}
+// groups of ranges of wgrad3x3_reduce_kernel: enough workgroups to fill the chip; each group costs one fp32 atomic per
+// element (deterministic mode: one group)
+int reduce_range_groups(int base, int split) {
+    const long e4 = (long)base * 9 * 1024;
+    int groups = (int)(512 / ((e4 + 255) / 256));
+    if (groups < 1 || combat_deterministic()) groups = 1;
+    if (groups > split) groups = split;
+    return groups;
+}
+
 int launch_reduce(const combat_wgrad_args *a, const W3dParams &p, hipStream_t st) {
     const int base = p.tiles_k * p.tiles_c;
-    // Default: the round-3 reduction (ranges dealt to <= 14 groups of workgroups, one fp32 atomic per element and group):
-    // 4-8 us back to back.  COMBAT_WGRAD_DET_REDUCE=1: reduce_slabs() as a launch of its own -- fixed summation order, no
-    // atomics, bit-reproducible -- 9-18 us (tools/wgrad_chain_bench.py): a workgroup owns whole elements, so the slabs
-    // of an element cannot be spread over the chip.
-    static const bool env_det = getenv("COMBAT_WGRAD_DET_REDUCE") != nullptr;
-    const bool det = combat_deterministic();
-    // deterministic mode: with >= 4 tiles (144 workgroups of 256 quads) ONE group of ranges fills enough of the chip
-    // and owns its elements (`dw += sum`, ranges in ascending order, no atomics): the round-3 kernel as it is; the
-    // 64-channel layers (one tile, up to 256 ranges) take reduce_slabs(), which spreads an element's slabs over lanes
-    const bool atomics = !env_det && (!det || base >= 4);
-    if (atomics) {
-        // enough workgroups to fill the chip; each group of ranges costs one fp32 atomic per element
+    if (reduce_by_ranges(base)) {
         const long e4 = (long)base * 9 * 1024;
-        int groups = (int)(512 / ((e4 + 255) / 256));
-        if (groups < 1 || det) groups = 1;
-        if (groups > p.split) groups = p.split;
-        COMBAT_LAUNCH(wgrad3x3_reduce_kernel, dim3((unsigned)((e4 + 255) / 256), groups), dim3(256), 0, st, p.ws, a->dw, base,
-                           p.tiles_c, p.split, a->k_real, a->c_real);
+        COMBAT_LAUNCH(wgrad3x3_reduce_kernel, dim3((unsigned)((e4 + 255) / 256), reduce_range_groups(base, p.split)), dim3(256), 0, st, p.ws,
+                      a->dw, base, p.tiles_c, p.split, a->k_real, a->c_real);
     } else {
         COMBAT_LAUNCH(wgrad3x3_reduce_det_kernel, dim3(256), dim3(256), 0, st, (const float *)p.ws, a->dw, base, p.tiles_c, p.split,
                            a->k_real, a->c_real);
@@ -717,3 +796,77 @@ int conv_wgrad3x3_dma_reduce(const combat_wgrad_args *a, hipStream_t st) {
     if (!w3d_plan(a, p) || !p.ws) return COMBAT_OK;
     return launch_reduce(a, p, st);
 }
+
+// ---- grouped launch: members[0..n) are problems of ONE geometry (include/combat_hip.h, combat_conv_wgrad_group)
+namespace {
+bool same_problem_shape(const combat_wgrad_args *a, const combat_wgrad_args *b) {
+    return a->N == b->N && a->H == b->H && a->W == b->W && a->C == b->C && a->P == b->P && a->Q == b->Q && a->K == b->K && a->R == b->R &&
+           a->S == b->S && a->stride == b->stride && a->pad == b->pad && a->k_real == b->k_real && a->c_real == b->c_real &&
+           a->split == b->split;
+}
+
+// bytes of ONE member's slab region (0: a single pixel range, no slabs), or -1 if the members do not form a group
+long group_member_bytes(const combat_wgrad_args *const *m, int n) {
+    if (!m || n < 1 || n > kGroupMax) return -1;
+    for (int i = 0; i < n; ++i) {
+        const combat_wgrad_args *a = m[i];
+        if (!a || !a->src || !a->dy || !a->dw || a->split < 0 || a->reduce_first || a->defer_reduce) return -1;
+        if (!same_problem_shape(m[0], a)) return -1;
+        for (int j = 0; j < i; ++j)
+            if (m[j]->dw == a->dw) return -1;      // (the reduction owns its elements: one member per gradient)
+    }
+    W3dParams p;
+    int smem;
+    if (!w3d_geometry(m[0], p, smem)) return -1;
+    return conv_wgrad3x3_dma_workspace(m[0]);
+}
+}  // namespace
+
+long conv_wgrad3x3_dma_group_workspace(const combat_wgrad_args *const *m, int n) {
+    const long one = group_member_bytes(m, n);
+    return one < 0 ? -1 : one * n;
+}
+
+// COMBAT_OK if launched, COMBAT_EINVAL (nothing launched) if the members are no group or the workspace is too small
+int conv_wgrad3x3_dma_group(const combat_wgrad_args *const *m, int n, void *workspace, long workspace_bytes, hipStream_t st) {
+    const long one = group_member_bytes(m, n);
+    if (one < 0 || (one > 0 && (!workspace || workspace_bytes < one * n))) return COMBAT_EINVAL;
+    // every member is planned as it would be alone (pick_split, per, slab layout), with region i of the workspace
+    W3dParams p;
+    W3dGroup g = {};
+    for (int i = 0; i < n; ++i) {
+        combat_wgrad_args b = *m[i];
+        b.workspace = one > 0 ? static_cast<char *>(workspace) + (size_t)i * one : nullptr;
+        b.workspace_bytes = one;
+        W3dParams q;
+        if (!w3d_plan(&b, q)) return COMBAT_EINVAL;
+        if (combat_deterministic() && !q.ws && q.split > 1) return COMBAT_EINVAL;
+        if (i == 0) p = q;
+        else if (q.split != p.split || q.per != p.per || (q.ws == nullptr) != (p.ws == nullptr)) return COMBAT_EINVAL;
+        g.src[i] = b.src;
+        g.dy[i] = b.dy;
+        g.dw[i] = b.dw;
+        g.ws[i] = q.ws;
+    }
+    fill_reduce_first(nullptr, p);
+    p.stamps = nullptr;
+    const int blocks = p.tiles_k * p.tiles_c * p.split;
+    int rc;
+    if (p.hpw == 2) rc = launch_w3d_group<2, 3>(p, g, blocks, n, st);
+    else if (p.hpw == 3) rc = launch_w3d_group<3, 2>(p, g, blocks, n, st);
+    else rc = launch_w3d_group<4, 2>(p, g, blocks, n, st);
+    if (rc != COMBAT_OK || !p.ws) return rc;
+    // one reduction launch over every member's slabs: launch_reduce()'s choice of form and grid, member = extra dimension
+    const combat_wgrad_args *a = m[0];
+    const int base = p.tiles_k * p.tiles_c;
+    if (reduce_by_ranges(base)) {
+        const long e4 = (long)base * 9 * 1024;
+        COMBAT_LAUNCH(wgrad3x3_reduce_group_kernel, dim3((unsigned)((e4 + 255) / 256), reduce_range_groups(base, p.split), n), dim3(256), 0,
+                      st, g, base, p.tiles_c, p.split, a->k_real, a->c_real);
+    } else {
+        COMBAT_LAUNCH(wgrad3x3_reduce_det_group_kernel, dim3(256, n), dim3(256), 0, st, g, base, p.tiles_c, p.split, a->k_real, a->c_real);
+    }
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+

@@ -52,6 +52,11 @@ class Plan:
     # deferral: 4.32, so it is not the slabs leaving the Infinity Cache) -- twenty event records between the auxiliary
     # queue's kernels and twenty cross-queue waits cost more than the 8-us reductions they take off that queue.
     defer_reduces = os.environ.get("COMBAT_DEFER_REDUCE", "0") == "1"
+    # Same-geometry weight gradients that follow each other on an auxiliary queue as ONE combat_conv_wgrad_group call
+    # (group_wgrads below).  COMBAT_WGRAD_GROUP = off | tail (only the plan's last run of layers: PreActResNet18's four
+    # layer1 convolutions) | pairs (two members at most, last stage only) | stages (every run inside a stage).  The
+    # default is what measured best on the alternated step: DESIGN.md section 5.
+    wgrad_groups = os.environ.get("COMBAT_WGRAD_GROUP", "stages")
 
     def __init__(self, name: str):
         self.name = name
@@ -246,6 +251,14 @@ class Plan:
                     rc = rc or lib.combat_conv_gemm(arg, st)
                     e1.record(stream)
                     prof.append((self.name + "/" + sub, arg._obj, e0, e1))
+            elif prof is not None and cfunc is lib.combat_conv_wgrad_group:   # its members' single launches, one at a time
+                rc = 0
+                for sub, arg in zip(what.split("+"), args[0]):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream)
+                    rc = rc or lib.combat_conv_wgrad(arg, st)
+                    e1.record(stream)
+                    prof.append((self.name + "/" + sub, arg.contents, e0, e1))
             elif prof is not None and (cfunc is lib.combat_conv_gemm or cfunc is lib.combat_conv_wgrad or
                                        cfunc is lib.combat_conv_wgrad_reduce):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -636,6 +649,91 @@ def balance_wgrads(plan: Plan, device) -> None:
 
 
 WGRAD_MAIN_TAIL = 0
+
+_WGRAD_GROUP_WS: Dict = {}
+
+
+def _wgrad_group_workspace(device, queue: int, need: int) -> torch.Tensor:
+    """The n slab regions of a queue's grouped weight gradients, sized from combat_conv_wgrad_group_workspace_bytes
+    (four members of 18.9 MB do not fit the 48 MB of _wgrad_workspace).  Per queue, like that one: the launches of a
+    queue run one after the other.  A plan holds the tensor it was built with, so growing never frees a region in use."""
+    key = (device, int(queue))
+    ws = _WGRAD_GROUP_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+        _WGRAD_GROUP_WS[key] = ws
+    return ws
+
+
+def group_wgrads(plan: Plan, device) -> None:
+    """Post-pass of a backward plan: runs of auxiliary-queue weight gradients of one geometry that the DMA-staged 3x3
+    kernel takes (the library decides: combat_conv_wgrad_group_workspace_bytes) become ONE combat_conv_wgrad_group
+    call -- one kernel launch of n x 128 workgroups and one reduction launch instead of n of each with a hand-off gap
+    between them.  The weight-gradient queue is what both training backward passes wait for at their end, when nothing
+    else is left to run beside it.
+    A run never crosses an all-reduce mark (the gradients above a mark must be final there) and holds only calls that
+    follow each other on their queue.  The group call takes the place of its LAST member, so its hand-off waits for the
+    last producer; the earlier members' operands are read later than they used to be, which is safe because they are
+    named Slot buffers (activations, 'g.*' gradients) that are written once per pass and never recycled inside a plan.
+    Each member keeps its own WgradArgs (plan.wgrads, the profiled replay), whose workspace field the group ignores."""
+    mode = Plan.wgrad_groups
+    if mode not in ("tail", "pairs", "stages") or Plan.serial:
+        return
+    cap = 2 if mode == "pairs" else 4
+    marks = sorted(plan.marks)
+    stage = lambda ci: sum(1 for m in marks if m < ci)
+    args_of = {ci: a for ci, a in plan.wgrads}
+    linked = set(plan.after) | set(plan.after.values())
+    PP = ctypes.POINTER(ops.WgradArgs)
+
+    def query(members):
+        arr = (PP * len(members))(*[ctypes.pointer(a) for a in members])
+        return arr, int(lib.combat_conv_wgrad_group_workspace_bytes(arr, len(members)))
+
+    runs, run = [], []
+    for ci in sorted(plan.aux):
+        a = args_of.get(ci)
+        ok = a is not None and plan.calls[ci][0] is lib.combat_conv_wgrad and ci not in linked
+        if ok and run and len(run) < cap and plan.aux[run[-1]] == plan.aux[ci] and stage(run[0]) == stage(ci) and \
+                query([args_of[c] for c in run] + [a])[1] >= 0:
+            run.append(ci)
+            continue
+        if len(run) > 1:
+            runs.append(run)
+        run = [ci] if ok and query([a])[1] >= 0 else []
+    if len(run) > 1:
+        runs.append(run)
+    if mode == "tail":
+        runs = runs[-1:]
+    elif mode == "pairs":
+        runs = [r for r in runs if stage(r[0]) == stage(runs[-1][0])]
+    if not runs:
+        return
+    replaced, dropped = {}, set()
+    for r in runs:
+        arr, need = query([args_of[c] for c in r])
+        ws = _wgrad_group_workspace(device, plan.aux[r[-1]], need)
+        plan.hold(arr, ws)
+        replaced[r[-1]] = (lib.combat_conv_wgrad_group, (arr, len(r), ws.data_ptr(), ws.numel()), "+".join(plan.calls[c][2] for c in r))
+        dropped.update(r[:-1])
+        for c in r[:-1]:
+            args_of[c] = None
+    assert not (dropped & set(plan.marks)), "an all-reduce mark on a weight-gradient call"
+    new_index, calls = {}, []
+    last_of = {c: r[-1] for r in runs for c in r}
+    for ci, call in enumerate(plan.calls):
+        if ci in dropped:
+            continue
+        new_index[ci] = len(calls)
+        calls.append(replaced.get(ci, call))
+    at = lambda ci: new_index[last_of.get(ci, ci)]
+    plan.calls = calls
+    plan.marks = {at(ci): off for ci, off in plan.marks.items()}
+    plan.aux = {at(ci): q for ci, q in plan.aux.items() if ci not in dropped}
+    plan.after = {at(ci): at(dep) for ci, dep in plan.after.items()}
+    plan.wgrads = [(at(ci), a) for ci, a in plan.wgrads]
+    plan.pending_reduces = [(w, a, at(ci)) for w, a, ci in plan.pending_reduces]
+    plan._prog = None
 
 
 _WGRAD_WS: Dict = {}
@@ -1222,6 +1320,7 @@ class PreActEngine(NetEngine):
         rec_wgrad(P, "stem.wgrad", self.input(slot), d_out, self.stem, fp.grad_phys("conv1.weight"), aux=False)
         P.mark(0)
         balance_wgrads(P, self.device)
+        group_wgrads(P, self.device)
         slot.plans[key] = P
         return P
 
@@ -1506,6 +1605,7 @@ class ResNetEngine(PreActEngine):
                 self._bwd_apply(P, slot, "g." + self.bn0.prefix, dz0, y0, dy0, st0)
                 rec_wgrad(P, "stem.wgrad", self.input(slot), dy0, self.stem, fp.grad_phys("conv1.weight"), aux=False)
         P.mark(0)
+        group_wgrads(P, self.device)
         slot.plans[key] = P
         return P
 
@@ -1781,6 +1881,7 @@ class UnetEngine(NetEngine):
         rec_wgrad(P, "conv0_0.wgrad", self.input(slot), d00, pc["conv0_0"], fp.grad_phys("conv0_0.weight"), aux=False)
         P.mark(0)
         balance_wgrads(P, self.device)
+        group_wgrads(P, self.device)
         slot.plans["bwd"] = P
         return P
 

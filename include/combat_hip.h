@@ -242,6 +242,23 @@ int combat_conv_wgrad(const combat_wgrad_args *a, void *stream);
 int combat_conv_wgrad_reduce(const combat_wgrad_args *a, void *stream);
 /* scratch bytes the launch for these args can use (0: none) */
 int64_t combat_conv_wgrad_workspace_bytes(const combat_wgrad_args *a);
+/* Grouped weight gradient: members[0..n), 1 <= n <= 4, are problems of ONE geometry (every scalar field equal; src, dy
+ * and dw differ, the dw pairwise distinct) that the DMA-staged 3x3 kernel takes (3x3 / stride 1 / pad 1, no prologue,
+ * C and K multiples of 64, split >= 0).  ONE kernel launch of n x (the workgroups a member gets alone) computes them and
+ * ONE reduction launch adds every member's partial sums: n - 1 kernel ramps, hand-offs and reduction launches less
+ * than n combat_conv_wgrad calls, and n times the workgroups for a chip that has nothing else to run.  Each member keeps
+ * the pixel ranges, slab layout and per-element summation order of its single launch: in deterministic mode its dw
+ * is bit-identical to combat_conv_wgrad(member) alone.
+ * workspace: combat_conv_wgrad_group_workspace_bytes(members, n) bytes (n equal regions, member i uses region i; the
+ * members' own workspace fields are ignored); 0 bytes are needed where a member has a single pixel range.
+ * Returns COMBAT_EINVAL and launches nothing for mixed geometries, a member another kernel would take, reduce_first or
+ * defer_reduce set on a member, or too little workspace: the caller groups only what fits.
+ * `members` (HOST array of HOST pointers) is read at launch time; a recorded plan keeps the pointer, so the array and
+ * the structs must stay alive for the plan's lifetime. */
+int combat_conv_wgrad_group(const combat_wgrad_args *const *members, int32_t n, void *workspace, int64_t workspace_bytes,
+                            void *stream);
+/* bytes combat_conv_wgrad_group needs for these members (>= 0), or COMBAT_EINVAL if they do not form a group */
+int64_t combat_conv_wgrad_group_workspace_bytes(const combat_wgrad_args *const *members, int32_t n);
 
 /* fp32 [K][taps][c_real] master weights -> bf16 packed operands.
  * wf: forward  [rows_pad(K)][kpad_f], k = tap*C + c   (C = padded channel count, hi/lo dup if dup_hilo)

@@ -411,7 +411,7 @@ def check_streams(streams, res=None):
             n = check_ws(symbol, args, events, res)
         elif name in ("conv_gather_dma_kernel", "conv_gather_dma_src2_kernel", "conv_gather_dma_pair_kernel"):
             n = check_gather(symbol, name, args, events, res)
-        elif name == "conv_wgrad3x3_dma_kernel":
+        elif name in ("conv_wgrad3x3_dma_kernel", "conv_wgrad3x3_dma_group_kernel"):   # (the grouped form: same patch loop)
             n = check_wgrad(symbol, args, events, res)
         else:
             continue
