@@ -341,6 +341,229 @@ __global__ __launch_bounds__(256) void trigger_groups_bwd_kernel(const float *__
                              0.f, pre_tanh, d_noise + (long)img * hw2 * 8);
 }
 
+// ------------------------------------------------------------------ planes too large for LDS (64 < hw <= 256: ImageNet-10)
+// One workgroup per (16-row strip, channel, image), as dct_u8_big_kernel; thread j owns column j of the strip (hw <= 256
+// threads work, all 256 reach the barriers).  No whole plane is ever in LDS: only one [R][hw] strip of an intermediate.
+//
+// strip_sandwich: m[r] = (P[rows] * W * P)[r][j] for the R rows row0 .. row0 + R - 1 (clamped into the plane: a clamped
+// row is a duplicate its caller ignores), where W[k][j] = right(k), asked for k = 0 .. hw - 1 in ascending order.
+//   T = P[rows] * W : the row of P is the same for every thread (read straight from global memory, a wave-uniform
+//                     load), W's column element comes from `right`; T goes to LDS (Ts, [R][hw])
+//   m = T * P       : P symmetric, so column j of P^T is read as P[k][j], unit stride across the threads
+// k ascends with one fma per term, as mm4.
+template <int R, typename F>
+__device__ __forceinline__ void strip_sandwich(float *Ts, const float *__restrict__ P, int hw, int row0, int j, bool on,
+                                               F right, float (&m)[R]) {
+    const float *prow[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) prow[r] = P + (long)min(max(row0 + r, 0), hw - 1) * hw;
+#pragma unroll
+    for (int r = 0; r < R; ++r) m[r] = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < hw; ++k) {
+        const float w = right(k);
+#pragma unroll
+        for (int r = 0; r < R; ++r) m[r] = fmaf(prow[r][k], w, m[r]);
+    }
+    if (on) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) Ts[r * hw + j] = m[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; ++r) m[r] = 0.f;
+    for (int k = 0; k < hw; k += 4) {         // hw % 16 == 0
+        const float p0 = P[(long)k * hw + j], p1 = P[(long)(k + 1) * hw + j], p2 = P[(long)(k + 2) * hw + j],
+                    p3 = P[(long)(k + 3) * hw + j];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const f32x4_t t = *reinterpret_cast<const f32x4_t *>(Ts + r * hw + k);
+            m[r] = fmaf(t[0], p0, m[r]);
+            m[r] = fmaf(t[1], p1, m[r]);
+            m[r] = fmaf(t[2], p2, m[r]);
+            m[r] = fmaf(t[3], p3, m[r]);
+        }
+    }
+    __syncthreads();      // Ts is free again
+}
+
+// Forward.  The blur crosses the strip's seams, so the strip computes the clamp-mix for its 16 rows and one halo row on
+// either side (rows r0 - 1 .. r0 + 16: 18/16 of the products; past the plane's edge the blur reflects onto rows the strip
+// holds anyway).  The rows' blur (Kb * bd) stays in the thread's registers -- it only combines values of one column --
+// and the columns' blur (* Kb^T) goes through LDS.  LDS: Ts [18][hw] floats.
+__global__ __launch_bounds__(256) void trigger_big_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                              const float *__restrict__ P, const float *__restrict__ k1,
+                                                              float rate, int hw, const int *__restrict__ src_index,
+                                                              float *__restrict__ out, __bf16 *__restrict__ out_c8) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, tid = threadIdx.x, r0 = blockIdx.x * 16, c = blockIdx.y, img = blockIdx.z;
+    const bool on = tid < hw;
+    const int j = on ? tid : hw - 1;
+    const long src = src_index ? src_index[img] : img;
+    const float *xi = x + (src * 3 + c) * hw2;
+    const __bf16 *nz = noise + src * hw2 * 8 + c;
+    const float kk[3] = {k1[0], k1[1], k1[2]};
+    float m[18];
+    strip_sandwich<18>(sm, P, hw, r0 - 1, j, on, [&](int k) { return (float)nz[((long)k * hw + j) * 8]; }, m);
+#pragma unroll
+    for (int r = 0; r < 18; ++r) {
+        const int row = min(max(r0 - 1 + r, 0), hw - 1);
+        m[r] = fminf(fmaxf(fmaf(m[r], rate, xi[row * hw + j]), -1.f), 1.f);
+    }
+    if (on) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {          // Kb * bd, row i = r0 + r: rows i - 1, i, i + 1 are m[r], m[r + 1], m[r + 2]
+            const int i = r0 + r;
+            float s = 0.f;
+            if (i > 0) s = fmaf(blur_coef(kk, hw, i, i - 1), m[r], s);
+            s = fmaf(blur_coef(kk, hw, i, i), m[r + 1], s);
+            if (i + 1 < hw) s = fmaf(blur_coef(kk, hw, i, i + 1), m[r + 2], s);
+            sm[r * hw + j] = s;
+        }
+    }
+    __syncthreads();
+    if (on) {
+        const float cm = j > 0 ? blur_coef(kk, hw, j, j - 1) : 0.f, c0 = blur_coef(kk, hw, j, j),
+                    cp = j + 1 < hw ? blur_coef(kk, hw, j, j + 1) : 0.f;
+        const int jm = j > 0 ? j - 1 : j, jp = j + 1 < hw ? j + 1 : j;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {          // ... * Kb^T
+            const float *row = sm + r * hw;
+            float s = 0.f;
+            if (j > 0) s = fmaf(cm, row[jm], s);
+            s = fmaf(c0, row[j], s);
+            if (j + 1 < hw) s = fmaf(cp, row[jp], s);
+            const long o = (long)(r0 + r) * hw + j;
+            out[((long)img * 3 + c) * hw2 + o] = s;
+            if (out_c8) store_hilo(out_c8 + ((long)img * hw2 + o) * 8, c, s);
+        }
+    }
+}
+
+// mse[3 img + c] = sum (out - x)^2 over the plane, a launch of its own behind trigger_big_fwd_kernel: one workgroup of
+// 1024 threads per plane, so the strips' shares meet in a fixed order (each thread adds its pixels in index order -- the
+// loads of seven of them in flight at a time --, the 64 lanes of a wave are folded by shuffles, the sixteen wave sums
+// added in wave order): the same bits on every run.
+__global__ __launch_bounds__(1024) void trigger_big_mse_kernel(const float *__restrict__ x, const float *__restrict__ out, int hw,
+                                                               const int *__restrict__ src_index, float *__restrict__ mse) {
+    __shared__ float ws[16];
+    const int hw2 = hw * hw, tid = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
+    const long src = src_index ? src_index[img] : img;
+    const float *xi = x + (src * 3 + c) * hw2, *oi = out + ((long)img * 3 + c) * hw2;
+    float se = 0.f;
+#pragma unroll 7
+    for (int o = tid; o < hw2; o += 1024) {
+        const float d = oi[o] - xi[o];
+        se = fmaf(d, d, se);
+    }
+    for (int d = 32; d > 0; d >>= 1) se += __shfl_down(se, d, 64);
+    if ((tid & 63) == 0) ws[tid >> 6] = se;
+    __syncthreads();
+    if (tid == 0) {
+        float t = ws[0];
+        for (int w = 1; w < 16; ++w) t += ws[w];
+        mse[img * 3 + c] = t;
+    }
+}
+
+// Backward, first launch: the clamp mask.  P * noise * P is recomputed (as trigger_bwd_kernel does), strip by strip, and
+// only whether x + rate * (...) lies inside [-1, 1] is kept: bit r of mask[((3 img + c) * hw / 16 + strip) * hw + j] is
+// pixel (16 strip + r, j).  hw^2 / 8 bytes per plane.  LDS: Ts [16][hw].
+__global__ __launch_bounds__(256) void trigger_big_mask_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                               const float *__restrict__ P, float rate, int hw,
+                                                               unsigned short *__restrict__ mask) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, tid = threadIdx.x, r0 = blockIdx.x * 16, c = blockIdx.y, img = blockIdx.z;
+    const bool on = tid < hw;
+    const int j = on ? tid : hw - 1;
+    const float *xi = x + ((long)img * 3 + c) * hw2;
+    const __bf16 *nz = noise + (long)img * hw2 * 8 + c;
+    float m[16];
+    strip_sandwich<16>(sm, P, hw, r0, j, on, [&](int k) { return (float)nz[((long)k * hw + j) * 8]; }, m);
+    unsigned bits = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float v = fmaf(m[r], rate, xi[(r0 + r) * hw + j]);
+        bits |= (v >= -1.f && v <= 1.f ? 1u : 0u) << r;
+    }
+    if (on) mask[(((long)img * 3 + c) * (hw >> 4) + blockIdx.x) * hw + j] = (unsigned short)bits;
+}
+
+// Backward, second launch: d_noise[strip] = P[strip] * W * P with W = rate * mask .* (Kb^T g Kb), g = d_out + d_out2 +
+// 2 l2 (out - x).  W is never stored: thread j walks down column j and forms W[k][j] from the mask bit and the 3 x 3
+// blur adjoint of g, whose three row terms (g Kb)[k - 1 .. k + 1][j] slide along in registers (one new row of three
+// pixels per k).  LDS: Ts [16][hw].
+__global__ __launch_bounds__(256) void trigger_big_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                              const float *__restrict__ P, const float *__restrict__ k1,
+                                                              float rate, int hw, const float *__restrict__ d_out,
+                                                              const float *__restrict__ d_out2,
+                                                              const float *__restrict__ outp, float l2_scale, int pre_tanh,
+                                                              const unsigned short *__restrict__ mask,
+                                                              __bf16 *__restrict__ d_noise) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, tid = threadIdx.x, r0 = blockIdx.x * 16, c = blockIdx.y, img = blockIdx.z;
+    const bool on = tid < hw;
+    const int j = on ? tid : hw - 1;
+    const long pl = ((long)img * 3 + c) * hw2;
+    const float *xi = x + pl, *g1 = d_out ? d_out + pl : nullptr, *g2 = d_out2 ? d_out2 + pl : nullptr,
+                *op = l2_scale != 0.f ? outp + pl : nullptr;
+    const unsigned short *mk = mask + ((long)img * 3 + c) * (hw >> 4) * hw + j;
+    const float kk[3] = {k1[0], k1[1], k1[2]};
+    // (g Kb)[a][j] = sum_b g[a][b] Kb[b][j], b = j - 1 .. j + 1 inside the plane, ascending
+    const int jm = j > 0 ? j - 1 : j, jp = j + 1 < hw ? j + 1 : j;
+    const float cm = j > 0 ? blur_coef(kk, hw, j - 1, j) : 0.f, c0 = blur_coef(kk, hw, j, j),
+                cp = j + 1 < hw ? blur_coef(kk, hw, j + 1, j) : 0.f;
+    auto g_at = [&](int o) {
+        float g = g1 ? g1[o] : 0.f;
+        if (g2) g += g2[o];
+        if (op) g = fmaf(2.f * l2_scale, op[o] - xi[o], g);
+        return g;
+    };
+    auto h_row = [&](int a) {
+        float s = 0.f;
+        if (j > 0) s = fmaf(cm, g_at(a * hw + jm), s);
+        s = fmaf(c0, g_at(a * hw + j), s);
+        if (j + 1 < hw) s = fmaf(cp, g_at(a * hw + jp), s);
+        return s;
+    };
+    float hm = 0.f, h0 = h_row(0), hp = h_row(1);
+    unsigned bits = 0;
+    float m[16];
+    strip_sandwich<16>(sm, P, hw, r0, j, on,
+                       [&](int k) {
+                           if ((k & 15) == 0) bits = mk[(long)(k >> 4) * hw];
+                           float s = 0.f;        // (Kb^T h)[k][j] = sum_a Kb[a][k] h[a][j], a = k - 1 .. k + 1, ascending
+                           if (k > 0) s = fmaf(blur_coef(kk, hw, k - 1, k), hm, s);
+                           s = fmaf(blur_coef(kk, hw, k, k), h0, s);
+                           if (k + 1 < hw) s = fmaf(blur_coef(kk, hw, k + 1, k), hp, s);
+                           const float w = (bits >> (k & 15)) & 1u ? s * rate : 0.f;
+                           hm = h0;
+                           h0 = hp;
+                           hp = k + 2 < hw ? h_row(k + 2) : 0.f;
+                           return w;
+                       },
+                       m);
+    if (on) {
+        const __bf16 *nz = noise + (long)img * hw2 * 8;
+        __bf16 *dn = d_noise + (long)img * hw2 * 8;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long o = (long)(r0 + r) * hw + j;
+            __bf16 *px = dn + o * 8;
+            float v = m[r];
+            if (pre_tanh) {  // noise = tanh(z): hand back the gradient w.r.t. z
+                const float t = (float)nz[o * 8 + c];
+                v *= 1.f - t * t;
+            }
+            px[c] = (__bf16)v;
+            if (c == 0) {   // channels 3..7 of the c8 pixel carry no gradient
+                px[3] = (__bf16)0.f;
+                *reinterpret_cast<uint2 *>(px + 4) = make_uint2(0u, 0u);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ augmentation
 struct AugGeom {
     float ca, sa, cx, cy;
@@ -609,8 +832,24 @@ extern "C" int combat_trigger_fwd(const float *x, const void *noise, const float
                                   float noise_rate, int32_t n, int32_t hw, const int32_t *src_index, float *out,
                                   void *out_c8, float *mse_partial, void *stream) {
     COMBAT_PLAN_HOOK(combat_trigger_fwd, x, noise, P, k1, noise_rate, n, hw, src_index, out, out_c8, mse_partial);
-    if (!x || !noise || !P || !k1 || !out || n < 0 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (!x || !noise || !P || !k1 || !out || n < 0 || hw < 16 || hw > 256 || (hw & 3) || (hw > 64 && (hw & 15))) return COMBAT_EINVAL;
     if (n == 0) return COMBAT_OK;
+    if (hw > 64) {      // strips: only the last launch of the call may carry a replayed plan's hand-off event
+        hipStream_t st = as_stream(stream);
+        if (mse_partial) {
+            hipLaunchKernelGGL(trigger_big_fwd_kernel, dim3(hw / 16, 3, n), dim3(256), 18 * hw * 4, st, x,
+                               reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, src_index, out,
+                               reinterpret_cast<__bf16 *>(out_c8));
+            CB_LAUNCH_CHECK();
+            COMBAT_LAUNCH(trigger_big_mse_kernel, dim3(3, n), dim3(1024), 0, st, x, (const float *)out, hw, src_index, mse_partial);
+        } else {
+            COMBAT_LAUNCH(trigger_big_fwd_kernel, dim3(hw / 16, 3, n), dim3(256), 18 * hw * 4, st, x,
+                          reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, src_index, out,
+                          reinterpret_cast<__bf16 *>(out_c8));
+        }
+        CB_LAUNCH_CHECK();
+        return COMBAT_OK;
+    }
     const int bytes = (4 * hw * hw + 2 * hw) * 4;
     if (set_smem(trigger_fwd_kernel, bytes)) return COMBAT_ELAUNCH;
     COMBAT_LAUNCH(trigger_fwd_kernel, dim3(3, n), dim3(256), bytes, as_stream(stream), x,
@@ -624,9 +863,39 @@ extern "C" int combat_trigger_bwd(const float *x, const void *noise, const float
                                   float noise_rate, int32_t n, int32_t hw, const float *d_out, const float *d_out2,
                                   const float *out, float l2_scale, int32_t pre_tanh, void *d_noise, void *stream) {
     COMBAT_PLAN_HOOK(combat_trigger_bwd, x, noise, P, k1, noise_rate, n, hw, d_out, d_out2, out, l2_scale, pre_tanh, d_noise);
-    if (!x || !noise || !P || !k1 || !d_noise || n < 0 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (!x || !noise || !P || !k1 || !d_noise || n < 0 || hw < 16 || hw > 256 || (hw & 3) || (hw > 64 && (hw & 15))) return COMBAT_EINVAL;
     if (l2_scale != 0.f && !out) return COMBAT_EINVAL;
     if (n == 0) return COMBAT_OK;
+    if (hw > 64) {
+        // the clamp mask (one bit per pixel) lives in this stream's scratch between the two launches; a batch whose mask
+        // does not fit is taken in runs of images, one pair of launches each (224 x 224: 111 images per run)
+        constexpr size_t kScratch = 2u << 20;
+        hipStream_t st = as_stream(stream);
+        const size_t plane = (size_t)hw * hw, per_img = 3 * plane / 8;
+        const int run = (int)(kScratch / per_img < (size_t)n ? kScratch / per_img : (size_t)n);
+        unsigned short *mask = reinterpret_cast<unsigned short *>(combat_stream_scratch(stream, (size_t)run * per_img));
+        if (!mask) return COMBAT_ELAUNCH;
+        for (int i0 = 0; i0 < n; i0 += run) {
+            const int ni = n - i0 < run ? n - i0 : run;
+            const size_t o3 = (size_t)i0 * 3 * plane, o8 = (size_t)i0 * plane * 8;
+            const __bf16 *nz = reinterpret_cast<const __bf16 *>(noise) + o8;
+            hipLaunchKernelGGL(trigger_big_mask_kernel, dim3(hw / 16, 3, ni), dim3(256), 16 * hw * 4, st, x + o3, nz, P,
+                               noise_rate, hw, mask);
+            CB_LAUNCH_CHECK();
+            if (i0 + ni < n)
+                hipLaunchKernelGGL(trigger_big_bwd_kernel, dim3(hw / 16, 3, ni), dim3(256), 16 * hw * 4, st, x + o3, nz, P, k1,
+                                   noise_rate, hw, d_out ? d_out + o3 : nullptr, d_out2 ? d_out2 + o3 : nullptr,
+                                   out ? out + o3 : nullptr, l2_scale, pre_tanh, (const unsigned short *)mask,
+                                   reinterpret_cast<__bf16 *>(d_noise) + o8);
+            else
+                COMBAT_LAUNCH(trigger_big_bwd_kernel, dim3(hw / 16, 3, ni), dim3(256), 16 * hw * 4, st, x + o3, nz, P, k1,
+                              noise_rate, hw, d_out ? d_out + o3 : nullptr, d_out2 ? d_out2 + o3 : nullptr,
+                              out ? out + o3 : nullptr, l2_scale, pre_tanh, (const unsigned short *)mask,
+                              reinterpret_cast<__bf16 *>(d_noise) + o8);
+            CB_LAUNCH_CHECK();
+        }
+        return COMBAT_OK;
+    }
     const int bytes = (5 * hw * hw + 2 * hw) * 4;
     if (set_smem(trigger_bwd_kernel, bytes)) return COMBAT_ELAUNCH;
     COMBAT_LAUNCH(trigger_bwd_kernel, dim3(3, n), dim3(256), bytes, as_stream(stream), x,
@@ -654,6 +923,7 @@ extern "C" int combat_trigger_tv_bwd(const float *x, const void *noise, const fl
                                      float noise_rate, int32_t n, int32_t hw, const float *d_out, const float *d_out2,
                                      const float *out, float l2_scale, float tv_scale, int32_t pre_tanh, void *d_noise,
                                      void *stream) {
+    if (hw > 64) return COMBAT_EINVAL;      // (combat_trigger_bwd's strip route has no total-variation form)
     if (tv_scale == 0.f)      // nothing to add: the launch of combat_trigger_bwd itself
         return combat_trigger_bwd(x, noise, P, k1, noise_rate, n, hw, d_out, d_out2, out, l2_scale, pre_tanh, d_noise, stream);
     COMBAT_PLAN_HOOK(combat_trigger_tv_bwd, x, noise, P, k1, noise_rate, n, hw, d_out, d_out2, out, l2_scale, tv_scale,

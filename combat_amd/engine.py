@@ -853,6 +853,17 @@ class NetEngine:
 
     # ---- normalisation plumbing -----------------------------------------------------------
     FUSED_DIRECT_PX = 1024   # pixels per group the fused norm kernels reduce themselves (kFusedMaxDirect, norm.hip)
+    FUSED_MAX_ROWS = 256     # partial rows per group they reduce themselves (kFusedMaxRows); more go through a first stage
+
+    def _norm_scratch(self, plan: Plan, groups: int, c: int, rows: int) -> torch.Tensor:
+        """Scratch for a finalize / fused launch over `rows` partial rows per group.  More than FUSED_MAX_ROWS rows
+        are first folded into combat_norm_scratch_bytes(groups, c) of it: instance statistics of 112 x 112 and
+        224 x 224 maps (392 and 1568 rows per image) at a batch size the engine's default region cannot hold get a
+        larger one, kept from then on.  (The launches of one engine run one after the other.)"""
+        if rows > self.FUSED_MAX_ROWS and ops.norm_scratch_bytes(groups, c) > self._scratch.numel() * 4:
+            self._scratch = torch.empty(ops.norm_scratch_bytes(groups, c) // 4, dtype=f32, device=self.device)
+        plan.hold(self._scratch)
+        return self._scratch
 
     def _conv_norm(self, plan: Plan, slot: Slot, key: str, src, dst, pc: PackedConv, *, groups: int,
                    gamma=None, beta=None, running=None, act_dst=None, slope: float = 0.0, defer: bool = False,
@@ -899,10 +910,10 @@ class NetEngine:
             if act_dst is not None:
                 self._norm_act(plan, st, act_dst, slope)
             return st
+        scr = self._norm_scratch(plan, groups, c, rpg)
         plan.add(key + ".finalize", lib.combat_norm_finalize, part.data_ptr(), groups, rpg, c, float(m // groups),
                  1e-5, _p(gamma), _p(beta), st.mean.data_ptr(), st.rstd.data_ptr(), st.scale.data_ptr(),
-                 st.shift.data_ptr(), _p(rm), _p(rv), 0.1, _p(nbt), self._scratch.data_ptr(),
-                 self._scratch.numel() * 4)
+                 st.shift.data_ptr(), _p(rm), _p(rv), 0.1, _p(nbt), scr.data_ptr(), scr.numel() * 4)
         return st
 
     def _lds_prologue_ok(self, src, pc: PackedConv) -> bool:
@@ -931,10 +942,11 @@ class NetEngine:
         st.pending = None
         x = q["x"]
         plan.hold(x, act_dst, q["part"])
+        scr = self._norm_scratch(plan, st.groups, st.C, q["rpg"])
         plan.add(q["key"] + ".finact", lib.combat_norm_act_fused, x.data_ptr(), _p(q["part"]), st.groups, q["rpg"],
                  q["pxg"], st.C, 1e-5, float(slope), _p(q["gamma"]), _p(q["beta"]), st.mean.data_ptr(),
                  st.rstd.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), _p(q["rm"]), _p(q["rv"]), 0.1,
-                 _p(q["nbt"]), self._scratch.data_ptr(), self._scratch.numel() * 4, act_dst.data_ptr())
+                 _p(q["nbt"]), scr.data_ptr(), scr.numel() * 4, act_dst.data_ptr())
 
     def _dgrad_norm(self, plan: Plan, slot: Slot, key: str, dy, dz, pc: PackedConv, x_pre, st: NormState, *,
                     group_stride: int, slope: float, gamma=None, dgamma=None, dbeta=None, add_pre=None, shortcut=None):
@@ -988,10 +1000,10 @@ class NetEngine:
         if part is None and (st.groups == 1 or pq > self.FUSED_DIRECT_PX):
             part, rpg = self._stats_bwd(plan, slot, key, dz, x_pre, st)
         plan.hold(dz, x_pre, dx, add, part, pend["gamma"], pend["dgamma"], pend["dbeta"])
+        scr = self._norm_scratch(plan, st.groups, c, rpg)
         plan.add(key + ".bfused", lib.combat_norm_bwd_fused, dz.data_ptr(), x_pre.data_ptr(), _p(add), _p(part),
                  st.groups, rpg, pxg, c, _p(pend["gamma"]), st.mean.data_ptr(), st.rstd.data_ptr(),
-                 _p(pend["dgamma"]), _p(pend["dbeta"]), self._scratch.data_ptr(), self._scratch.numel() * 4,
-                 dx.data_ptr())
+                 _p(pend["dgamma"]), _p(pend["dbeta"]), scr.data_ptr(), scr.numel() * 4, dx.data_ptr())
 
 
 # --------------------------------------------------------------------------------------------
@@ -1760,6 +1772,16 @@ class UnetEngine(NetEngine):
         def up(level, y, sy, skip, ss, s_in, c):
             o = slot.buf("up%d" % level, (n, 2 * s_in, 2 * s_in, c))
             P.hold(y, skip)
+            if sy.pending is not None and sy.pending["rpg"] > self.FUSED_MAX_ROWS:
+                # more partial rows than the fused launch takes (112 x 112 maps of 224 x 224 images: 392 per image):
+                # the statistics are finalised by a launch of their own, the upsampling reads scale / shift below
+                q = sy.pending
+                sy.pending = None
+                scr = self._norm_scratch(P, n, c, q["rpg"])
+                P.hold(q["part"])
+                P.add("up%d.finalize" % level, lib.combat_norm_finalize, q["part"].data_ptr(), n, q["rpg"], c,
+                      float(s_in * s_in), 1e-5, None, None, sy.mean.data_ptr(), sy.rstd.data_ptr(), sy.scale.data_ptr(),
+                      sy.shift.data_ptr(), None, None, 0.1, None, scr.data_ptr(), scr.numel() * 4)
             if sy.pending is not None:   # y's InstanceNorm is finalised by the launch that upsamples it
                 q = sy.pending
                 sy.pending = None

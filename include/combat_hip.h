@@ -407,6 +407,11 @@ int combat_unet_up_fused(const void *y, const float *partials, int32_t rows_per_
  * Backward: d_noise (bf16 NHWC c8) from d_out (fp32 NCHW) [+ 2*l2_scale*(out-x) MSE term];
  * pre_tanh != 0 multiplies by (1 - noise^2), i.e. returns the gradient w.r.t. the generator's
  * pre-tanh output (networks/models.py:340).
+ * hw: 16 .. 64 in steps of 4 (one workgroup per plane, everything in LDS), or 80 .. 256 in steps of 16 (ImageNet-10's
+ * 224: one workgroup per 16-row strip of a plane; P must be symmetric there, as oracle.lowpass_matrix is; mse_partial
+ * comes from a second launch of the same call, the backward's clamp mask -- one bit per pixel -- passes through the
+ * library's per-stream scratch between its two launches).  Anything else: COMBAT_EINVAL.  The _pair, _groups and _tv
+ * variants below take hw <= 64 only.
  * ------------------------------------------------------------------------------------------ */
 int combat_trigger_fwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
                        int32_t n, int32_t hw, const int32_t *src_index /* NULL, or output image i is made from row

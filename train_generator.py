@@ -4,7 +4,8 @@ Drop-in for the reference script of the same name: same flags (config.py), same
 ``get_model`` / ``train`` / ``eval`` / ``main`` call signatures, same checkpoint path and keys
 (reference train_generator.py:80-128, 131-318, 321-465, 468-609) -- the per-batch loop body
 (:170-290) runs as ``combat_amd.step.AlternatedStep`` on the HIP kernels.  CIFAR-10 + the default
-default classifier of the dataset (PreActResNet18 for cifar10, ResNet18 for celeba) / UNet / "original" detector;
+default classifier of the dataset (PreActResNet18 for cifar10, ResNet18 for celeba and for imagenet10 at 224 x 224,
+bs 32) / UNet / "original" detector (imagenet10: none ships, pass --allow_missing_F);
 other --model / --dataset values raise.  ``main()`` and ``train()`` are composed from ``combat_amd.run``, the frame
 every training script shares; what is this script's own is its tables, ``get_model`` and ``eval``.
 
