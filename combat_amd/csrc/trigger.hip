@@ -387,22 +387,36 @@ __device__ __forceinline__ void strip_sandwich(float *Ts, const float *__restric
     __syncthreads();      // Ts is free again
 }
 
+// What one (strip, channel, output row) of the strip kernels works on.  The plain, paired and grouped kernels differ only
+// in how they fill it from their block index (as the whole-plane wrappers differ around trigger_fwd_plane /
+// trigger_bwd_plane), so a paired launch writes the bits of two plain calls and a grouped one the bits of one plain call
+// per chunk.  Every field is the same for all threads of a workgroup: the pointers stay in scalar registers and the
+// blur coefficients the threads derive from k1 stay loop-invariant.
+struct StripRow {
+    const float *xi;             // channel c's plane of the image of x this row is made from
+    const __bf16 *nz;            // this row's noise pixels (c8)
+    const float *k1;             // its blur triple
+    float *out;                  // forward: channel c's plane of its output image
+    __bf16 *out_c8;              // forward: its output pixels as hi/lo c8 (may be null)
+    const float *g1, *g2;        // backward: channel c's planes of its gradients (either may be null)
+    const float *op;             // backward: channel c's plane of its output, null without the L2 term
+    float l2_scale;
+    unsigned short *mask;        // backward: its clamp-mask plane in the scratch, [hw / 16][hw]
+    __bf16 *dn;                  // backward: its gradient pixels (c8)
+};
+
 // Forward.  The blur crosses the strip's seams, so the strip computes the clamp-mix for its 16 rows and one halo row on
 // either side (rows r0 - 1 .. r0 + 16: 18/16 of the products; past the plane's edge the blur reflects onto rows the strip
 // holds anyway).  The rows' blur (Kb * bd) stays in the thread's registers -- it only combines values of one column --
 // and the columns' blur (* Kb^T) goes through LDS.  LDS: Ts [18][hw] floats.
-__global__ __launch_bounds__(256) void trigger_big_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
-                                                              const float *__restrict__ P, const float *__restrict__ k1,
-                                                              float rate, int hw, const int *__restrict__ src_index,
-                                                              float *__restrict__ out, __bf16 *__restrict__ out_c8) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int hw2 = hw * hw, tid = threadIdx.x, r0 = blockIdx.x * 16, c = blockIdx.y, img = blockIdx.z;
+__device__ __forceinline__ void trigger_big_fwd_strip(float *sm, const float *__restrict__ P, float rate, int hw, int r0, int c,
+                                                      const StripRow &w) {
+    const int tid = threadIdx.x;
     const bool on = tid < hw;
     const int j = on ? tid : hw - 1;
-    const long src = src_index ? src_index[img] : img;
-    const float *xi = x + (src * 3 + c) * hw2;
-    const __bf16 *nz = noise + src * hw2 * 8 + c;
-    const float kk[3] = {k1[0], k1[1], k1[2]};
+    const float *xi = w.xi;
+    const __bf16 *nz = w.nz + c;
+    const float kk[3] = {w.k1[0], w.k1[1], w.k1[2]};
     float m[18];
     strip_sandwich<18>(sm, P, hw, r0 - 1, j, on, [&](int k) { return (float)nz[((long)k * hw + j) * 8]; }, m);
 #pragma unroll
@@ -434,10 +448,58 @@ __global__ __launch_bounds__(256) void trigger_big_fwd_kernel(const float *__res
             s = fmaf(c0, row[j], s);
             if (j + 1 < hw) s = fmaf(cp, row[jp], s);
             const long o = (long)(r0 + r) * hw + j;
-            out[((long)img * 3 + c) * hw2 + o] = s;
-            if (out_c8) store_hilo(out_c8 + ((long)img * hw2 + o) * 8, c, s);
+            w.out[o] = s;
+            if (w.out_c8) store_hilo(w.out_c8 + o * 8, c, s);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void trigger_big_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                              const float *__restrict__ P, const float *__restrict__ k1,
+                                                              float rate, int hw, const int *__restrict__ src_index,
+                                                              float *__restrict__ out, __bf16 *__restrict__ out_c8) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.y, img = blockIdx.z;
+    const long src = src_index ? src_index[img] : img;      // row of x / noise this output image is made from
+    StripRow w = {};
+    w.xi = x + (src * 3 + c) * hw2;
+    w.nz = noise + src * hw2 * 8;
+    w.k1 = k1;
+    w.out = out + ((long)img * 3 + c) * hw2;
+    w.out_c8 = out_c8 ? out_c8 + (long)img * hw2 * 8 : nullptr;
+    trigger_big_fwd_strip(sm, P, rate, hw, blockIdx.x * 16, c, w);
+}
+
+// The paired trigger (trigger_pair_fwd_kernel) on strips: grid z = 2n rows, row i < n -> out_bd[i] with k1[0], row n + i
+// -> out_cross[i] = T(x[i], noise[n + i], k1[1]).  The squared-error partials of the first half come from
+// trigger_big_mse_kernel over out_bd.
+__global__ __launch_bounds__(256) void trigger_big_pair_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                                   const float *__restrict__ P, const float *__restrict__ k1,
+                                                                   float rate, int n, int hw, float *__restrict__ out_bd,
+                                                                   float *__restrict__ out_cross) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.y, row = blockIdx.z;
+    const int cross = row >= n, img = cross ? row - n : row;
+    StripRow w = {};
+    w.xi = x + ((long)img * 3 + c) * hw2;
+    w.nz = noise + (long)row * hw2 * 8;
+    w.k1 = k1 + 3 * cross;
+    w.out = (cross ? out_cross : out_bd) + ((long)img * 3 + c) * hw2;
+    trigger_big_fwd_strip(sm, P, rate, hw, blockIdx.x * 16, c, w);
+}
+
+// The grouped trigger (trigger_groups_fwd_kernel) on strips: image i is blurred with k1[i / ps].
+__global__ __launch_bounds__(256) void trigger_big_groups_fwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                                     const float *__restrict__ P, const float *__restrict__ k1,
+                                                                     float rate, int hw, int ps, float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.y, img = blockIdx.z;
+    StripRow w = {};
+    w.xi = x + ((long)img * 3 + c) * hw2;
+    w.nz = noise + (long)img * hw2 * 8;
+    w.k1 = k1 + 3 * (img / ps);
+    w.out = out + ((long)img * 3 + c) * hw2;
+    trigger_big_fwd_strip(sm, P, rate, hw, blockIdx.x * 16, c, w);
 }
 
 // mse[3 img + c] = sum (out - x)^2 over the plane, a launch of its own behind trigger_big_fwd_kernel: one workgroup of
@@ -467,17 +529,15 @@ __global__ __launch_bounds__(1024) void trigger_big_mse_kernel(const float *__re
 }
 
 // Backward, first launch: the clamp mask.  P * noise * P is recomputed (as trigger_bwd_kernel does), strip by strip, and
-// only whether x + rate * (...) lies inside [-1, 1] is kept: bit r of mask[((3 img + c) * hw / 16 + strip) * hw + j] is
-// pixel (16 strip + r, j).  hw^2 / 8 bytes per plane.  LDS: Ts [16][hw].
-__global__ __launch_bounds__(256) void trigger_big_mask_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
-                                                               const float *__restrict__ P, float rate, int hw,
-                                                               unsigned short *__restrict__ mask) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int hw2 = hw * hw, tid = threadIdx.x, r0 = blockIdx.x * 16, c = blockIdx.y, img = blockIdx.z;
+// only whether x + rate * (...) lies inside [-1, 1] is kept: bit r of mask[((3 row + c) * hw / 16 + strip) * hw + j] is
+// pixel (16 strip + r, j) of the launch's row `row` (grid z).  hw^2 / 8 bytes per plane.  LDS: Ts [16][hw].
+__device__ __forceinline__ void trigger_big_mask_strip(float *sm, const float *__restrict__ P, float rate, int hw, int strip,
+                                                       int c, const StripRow &w) {
+    const int tid = threadIdx.x, r0 = strip * 16;
     const bool on = tid < hw;
     const int j = on ? tid : hw - 1;
-    const float *xi = x + ((long)img * 3 + c) * hw2;
-    const __bf16 *nz = noise + (long)img * hw2 * 8 + c;
+    const float *xi = w.xi;
+    const __bf16 *nz = w.nz + c;
     float m[16];
     strip_sandwich<16>(sm, P, hw, r0, j, on, [&](int k) { return (float)nz[((long)k * hw + j) * 8]; }, m);
     unsigned bits = 0;
@@ -486,29 +546,50 @@ __global__ __launch_bounds__(256) void trigger_big_mask_kernel(const float *__re
         const float v = fmaf(m[r], rate, xi[(r0 + r) * hw + j]);
         bits |= (v >= -1.f && v <= 1.f ? 1u : 0u) << r;
     }
-    if (on) mask[(((long)img * 3 + c) * (hw >> 4) + blockIdx.x) * hw + j] = (unsigned short)bits;
+    if (on) w.mask[(long)strip * hw + j] = (unsigned short)bits;
+}
+
+__global__ __launch_bounds__(256) void trigger_big_mask_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                               const float *__restrict__ P, float rate, int hw,
+                                                               unsigned short *__restrict__ mask) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.y, img = blockIdx.z;
+    StripRow w = {};
+    w.xi = x + ((long)img * 3 + c) * hw2;
+    w.nz = noise + (long)img * hw2 * 8;
+    w.mask = mask + ((long)img * 3 + c) * (hw >> 4) * hw;
+    trigger_big_mask_strip(sm, P, rate, hw, blockIdx.x, c, w);
+}
+
+// The mask of rows row0 .. row0 + gridDim.z - 1 of the paired trigger's 2n rows: one run of the launcher.  x and noise
+// are the call's own pointers, because a run may begin in the first half and end in the cross half: x is indexed by
+// row mod n, the noise by row, the mask plane by the row's place in the run.
+__global__ __launch_bounds__(256) void trigger_big_pair_mask_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                                    const float *__restrict__ P, float rate, int n, int row0,
+                                                                    int hw, unsigned short *__restrict__ mask) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.y, row = row0 + blockIdx.z;
+    const int img = row >= n ? row - n : row;
+    StripRow w = {};
+    w.xi = x + ((long)img * 3 + c) * hw2;
+    w.nz = noise + (long)row * hw2 * 8;
+    w.mask = mask + ((long)blockIdx.z * 3 + c) * (hw >> 4) * hw;
+    trigger_big_mask_strip(sm, P, rate, hw, blockIdx.x, c, w);
 }
 
 // Backward, second launch: d_noise[strip] = P[strip] * W * P with W = rate * mask .* (Kb^T g Kb), g = d_out + d_out2 +
 // 2 l2 (out - x).  W is never stored: thread j walks down column j and forms W[k][j] from the mask bit and the 3 x 3
 // blur adjoint of g, whose three row terms (g Kb)[k - 1 .. k + 1][j] slide along in registers (one new row of three
 // pixels per k).  LDS: Ts [16][hw].
-__global__ __launch_bounds__(256) void trigger_big_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
-                                                              const float *__restrict__ P, const float *__restrict__ k1,
-                                                              float rate, int hw, const float *__restrict__ d_out,
-                                                              const float *__restrict__ d_out2,
-                                                              const float *__restrict__ outp, float l2_scale, int pre_tanh,
-                                                              const unsigned short *__restrict__ mask,
-                                                              __bf16 *__restrict__ d_noise) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int hw2 = hw * hw, tid = threadIdx.x, r0 = blockIdx.x * 16, c = blockIdx.y, img = blockIdx.z;
+__device__ __forceinline__ void trigger_big_bwd_strip(float *sm, const float *__restrict__ P, float rate, int hw, int r0, int c,
+                                                      int pre_tanh, const StripRow &w) {
+    const int tid = threadIdx.x;
     const bool on = tid < hw;
     const int j = on ? tid : hw - 1;
-    const long pl = ((long)img * 3 + c) * hw2;
-    const float *xi = x + pl, *g1 = d_out ? d_out + pl : nullptr, *g2 = d_out2 ? d_out2 + pl : nullptr,
-                *op = l2_scale != 0.f ? outp + pl : nullptr;
-    const unsigned short *mk = mask + ((long)img * 3 + c) * (hw >> 4) * hw + j;
-    const float kk[3] = {k1[0], k1[1], k1[2]};
+    const float *xi = w.xi, *g1 = w.g1, *g2 = w.g2, *op = w.op;
+    const float l2_scale = w.l2_scale;
+    const unsigned short *mk = w.mask + j;
+    const float kk[3] = {w.k1[0], w.k1[1], w.k1[2]};
     // (g Kb)[a][j] = sum_b g[a][b] Kb[b][j], b = j - 1 .. j + 1 inside the plane, ascending
     const int jm = j > 0 ? j - 1 : j, jp = j + 1 < hw ? j + 1 : j;
     const float cm = j > 0 ? blur_coef(kk, hw, j - 1, j) : 0.f, c0 = blur_coef(kk, hw, j, j),
@@ -536,16 +617,16 @@ __global__ __launch_bounds__(256) void trigger_big_bwd_kernel(const float *__res
                            if (k > 0) s = fmaf(blur_coef(kk, hw, k - 1, k), hm, s);
                            s = fmaf(blur_coef(kk, hw, k, k), h0, s);
                            if (k + 1 < hw) s = fmaf(blur_coef(kk, hw, k + 1, k), hp, s);
-                           const float w = (bits >> (k & 15)) & 1u ? s * rate : 0.f;
+                           const float wv = (bits >> (k & 15)) & 1u ? s * rate : 0.f;
                            hm = h0;
                            h0 = hp;
                            hp = k + 2 < hw ? h_row(k + 2) : 0.f;
-                           return w;
+                           return wv;
                        },
                        m);
     if (on) {
-        const __bf16 *nz = noise + (long)img * hw2 * 8;
-        __bf16 *dn = d_noise + (long)img * hw2 * 8;
+        const __bf16 *nz = w.nz;
+        __bf16 *dn = w.dn;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const long o = (long)(r0 + r) * hw + j;
@@ -562,6 +643,84 @@ __global__ __launch_bounds__(256) void trigger_big_bwd_kernel(const float *__res
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void trigger_big_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                              const float *__restrict__ P, const float *__restrict__ k1,
+                                                              float rate, int hw, const float *__restrict__ d_out,
+                                                              const float *__restrict__ d_out2,
+                                                              const float *__restrict__ outp, float l2_scale, int pre_tanh,
+                                                              const unsigned short *__restrict__ mask,
+                                                              __bf16 *__restrict__ d_noise) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.y, img = blockIdx.z;
+    const long pl = ((long)img * 3 + c) * hw2;
+    StripRow w = {};
+    w.xi = x + pl;
+    w.nz = noise + (long)img * hw2 * 8;
+    w.k1 = k1;
+    w.g1 = d_out ? d_out + pl : nullptr;
+    w.g2 = d_out2 ? d_out2 + pl : nullptr;
+    w.op = l2_scale != 0.f ? outp + pl : nullptr;
+    w.l2_scale = l2_scale;
+    w.mask = const_cast<unsigned short *>(mask) + ((long)img * 3 + c) * (hw >> 4) * hw;
+    w.dn = d_noise + (long)img * hw2 * 8;
+    trigger_big_bwd_strip(sm, P, rate, hw, blockIdx.x * 16, c, pre_tanh, w);
+}
+
+// Rows row0 .. row0 + gridDim.z - 1 of the paired backward (trigger_pair_bwd_kernel on strips), behind
+// trigger_big_pair_mask_kernel over the same rows.  Row i < n: d_bd (+ d_bd2) and the L2 term on out_bd, blur k1[0];
+// row n + i: d_cross alone, blur k1[1].
+__global__ __launch_bounds__(256) void trigger_big_pair_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                                   const float *__restrict__ P, const float *__restrict__ k1,
+                                                                   float rate, int n, int row0, int hw,
+                                                                   const float *__restrict__ d_bd, const float *__restrict__ d_bd2,
+                                                                   const float *__restrict__ out_bd, float l2_scale,
+                                                                   const float *__restrict__ d_cross, int pre_tanh,
+                                                                   const unsigned short *__restrict__ mask,
+                                                                   __bf16 *__restrict__ d_noise) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.y, row = row0 + blockIdx.z;
+    const int cross = row >= n, img = cross ? row - n : row;
+    const long pl = ((long)img * 3 + c) * hw2;
+    const float *g1 = cross ? d_cross : d_bd, *g2 = cross ? nullptr : d_bd2;
+    StripRow w = {};
+    w.xi = x + pl;
+    w.nz = noise + (long)row * hw2 * 8;
+    w.k1 = k1 + 3 * cross;
+    w.g1 = g1 ? g1 + pl : nullptr;
+    w.g2 = g2 ? g2 + pl : nullptr;
+    w.l2_scale = cross ? 0.f : l2_scale;
+    w.op = w.l2_scale != 0.f ? out_bd + pl : nullptr;
+    w.mask = const_cast<unsigned short *>(mask) + ((long)blockIdx.z * 3 + c) * (hw >> 4) * hw;
+    w.dn = d_noise + (long)row * hw2 * 8;
+    trigger_big_bwd_strip(sm, P, rate, hw, blockIdx.x * 16, c, pre_tanh, w);
+}
+
+// Images img0 .. img0 + gridDim.z - 1 of the grouped backward (trigger_groups_bwd_kernel on strips), behind
+// trigger_big_mask_kernel over the same images: image i is blurred with k1[i / ps], i counted over the whole call.
+__global__ __launch_bounds__(256) void trigger_big_groups_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                                     const float *__restrict__ P, const float *__restrict__ k1,
+                                                                     float rate, int hw, int ps, int img0,
+                                                                     const float *__restrict__ d_out,
+                                                                     const float *__restrict__ d_out2,
+                                                                     const float *__restrict__ outp, float l2_scale,
+                                                                     int pre_tanh, const unsigned short *__restrict__ mask,
+                                                                     __bf16 *__restrict__ d_noise) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.y, img = img0 + blockIdx.z;
+    const long pl = ((long)img * 3 + c) * hw2;
+    StripRow w = {};
+    w.xi = x + pl;
+    w.nz = noise + (long)img * hw2 * 8;
+    w.k1 = k1 + 3 * (img / ps);
+    w.g1 = d_out ? d_out + pl : nullptr;
+    w.g2 = d_out2 ? d_out2 + pl : nullptr;
+    w.op = l2_scale != 0.f ? outp + pl : nullptr;
+    w.l2_scale = l2_scale;
+    w.mask = const_cast<unsigned short *>(mask) + ((long)blockIdx.z * 3 + c) * (hw >> 4) * hw;
+    w.dn = d_noise + (long)img * hw2 * 8;
+    trigger_big_bwd_strip(sm, P, rate, hw, blockIdx.x * 16, c, pre_tanh, w);
 }
 
 // ------------------------------------------------------------------ augmentation
@@ -826,6 +985,20 @@ int set_smem(K kern, int bytes) {
                : COMBAT_ELAUNCH;
 }
 
+// The strip backwards' clamp mask (3 hw^2 / 8 bytes per image row) in the stream's 2 MB scratch: how many of `rows` rows
+// one run takes (all of them, or as many as fit).  mask is null if the scratch could not be had.
+struct BigRuns {
+    unsigned short *mask;
+    int run;
+};
+
+BigRuns big_runs(void *stream, int hw, size_t rows) {
+    constexpr size_t kScratch = 2u << 20;
+    const size_t per_row = 3 * (size_t)hw * hw / 8;
+    const int run = (int)(kScratch / per_row < rows ? kScratch / per_row : rows);
+    return {reinterpret_cast<unsigned short *>(combat_stream_scratch(stream, (size_t)run * per_row)), run};
+}
+
 }  // namespace
 
 extern "C" int combat_trigger_fwd(const float *x, const void *noise, const float *P, const float *k1,
@@ -869,11 +1042,11 @@ extern "C" int combat_trigger_bwd(const float *x, const void *noise, const float
     if (hw > 64) {
         // the clamp mask (one bit per pixel) lives in this stream's scratch between the two launches; a batch whose mask
         // does not fit is taken in runs of images, one pair of launches each (224 x 224: 111 images per run)
-        constexpr size_t kScratch = 2u << 20;
         hipStream_t st = as_stream(stream);
-        const size_t plane = (size_t)hw * hw, per_img = 3 * plane / 8;
-        const int run = (int)(kScratch / per_img < (size_t)n ? kScratch / per_img : (size_t)n);
-        unsigned short *mask = reinterpret_cast<unsigned short *>(combat_stream_scratch(stream, (size_t)run * per_img));
+        const size_t plane = (size_t)hw * hw;
+        const BigRuns rn = big_runs(stream, hw, (size_t)n);
+        unsigned short *mask = rn.mask;
+        const int run = rn.run;
         if (!mask) return COMBAT_ELAUNCH;
         for (int i0 = 0; i0 < n; i0 += run) {
             const int ni = n - i0 < run ? n - i0 : run;
@@ -943,8 +1116,23 @@ extern "C" int combat_trigger_pair_fwd(const float *x, const void *noise, const 
                                        float noise_rate, int32_t n, int32_t hw, float *out_bd, float *out_cross,
                                        float *mse_partial, void *stream) {
     COMBAT_PLAN_HOOK(combat_trigger_pair_fwd, x, noise, P, k1, noise_rate, n, hw, out_bd, out_cross, mse_partial);
-    if (!x || !noise || !P || !k1 || !out_bd || !out_cross || n < 0 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (!x || !noise || !P || !k1 || !out_bd || !out_cross || n < 0 || hw < 16 || hw > 256 || (hw & 3) || (hw > 64 && (hw & 15))) return COMBAT_EINVAL;
     if (n == 0) return COMBAT_OK;
+    if (hw > 64) {      // strips, as combat_trigger_fwd: 2n rows in one launch, the partials of the first n behind it
+        hipStream_t st = as_stream(stream);
+        if (mse_partial) {
+            hipLaunchKernelGGL(trigger_big_pair_fwd_kernel, dim3(hw / 16, 3, 2 * n), dim3(256), 18 * hw * 4, st, x,
+                               reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, n, hw, out_bd, out_cross);
+            CB_LAUNCH_CHECK();
+            COMBAT_LAUNCH(trigger_big_mse_kernel, dim3(3, n), dim3(1024), 0, st, x, (const float *)out_bd, hw,
+                          (const int *)nullptr, mse_partial);
+        } else {
+            COMBAT_LAUNCH(trigger_big_pair_fwd_kernel, dim3(hw / 16, 3, 2 * n), dim3(256), 18 * hw * 4, st, x,
+                          reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, n, hw, out_bd, out_cross);
+        }
+        CB_LAUNCH_CHECK();
+        return COMBAT_OK;
+    }
     const int bytes = (4 * hw * hw + 2 * hw) * 4;
     if (set_smem(trigger_pair_fwd_kernel, bytes)) return COMBAT_ELAUNCH;
     COMBAT_LAUNCH(trigger_pair_fwd_kernel, dim3(3, 2 * n), dim3(256), bytes, as_stream(stream), x,
@@ -959,9 +1147,35 @@ extern "C" int combat_trigger_pair_bwd(const float *x, const void *noise, const 
                                        void *d_noise, void *stream) {
     COMBAT_PLAN_HOOK(combat_trigger_pair_bwd, x, noise, P, k1, noise_rate, n, hw, d_bd, d_bd2, out_bd, l2_scale, d_cross,
                      pre_tanh, d_noise);
-    if (!x || !noise || !P || !k1 || !d_noise || n < 0 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (!x || !noise || !P || !k1 || !d_noise || n < 0 || hw < 16 || hw > 256 || (hw & 3) || (hw > 64 && (hw & 15))) return COMBAT_EINVAL;
     if (l2_scale != 0.f && !out_bd) return COMBAT_EINVAL;
     if (n == 0) return COMBAT_OK;
+    if (hw > 64) {
+        // as combat_trigger_bwd, over the 2n rows: the clamp mask of a run of rows in this stream's scratch, one pair of
+        // launches per run (224 x 224: 111 rows per run).  A run may straddle the two halves, so the kernels take the
+        // call's own pointers and the run's first row.
+        hipStream_t st = as_stream(stream);
+        const BigRuns rn = big_runs(stream, hw, 2 * (size_t)n);
+        if (!rn.mask) return COMBAT_ELAUNCH;
+        const __bf16 *nz = reinterpret_cast<const __bf16 *>(noise);
+        const int rows = 2 * n;
+        for (int r0 = 0; r0 < rows; r0 += rn.run) {
+            const int nr = rows - r0 < rn.run ? rows - r0 : rn.run;
+            hipLaunchKernelGGL(trigger_big_pair_mask_kernel, dim3(hw / 16, 3, nr), dim3(256), 16 * hw * 4, st, x, nz, P,
+                               noise_rate, n, r0, hw, rn.mask);
+            CB_LAUNCH_CHECK();
+            if (r0 + nr < rows)
+                hipLaunchKernelGGL(trigger_big_pair_bwd_kernel, dim3(hw / 16, 3, nr), dim3(256), 16 * hw * 4, st, x, nz, P, k1,
+                                   noise_rate, n, r0, hw, d_bd, d_bd2, out_bd, l2_scale, d_cross, pre_tanh,
+                                   (const unsigned short *)rn.mask, reinterpret_cast<__bf16 *>(d_noise));
+            else
+                COMBAT_LAUNCH(trigger_big_pair_bwd_kernel, dim3(hw / 16, 3, nr), dim3(256), 16 * hw * 4, st, x, nz, P, k1,
+                              noise_rate, n, r0, hw, d_bd, d_bd2, out_bd, l2_scale, d_cross, pre_tanh,
+                              (const unsigned short *)rn.mask, reinterpret_cast<__bf16 *>(d_noise));
+            CB_LAUNCH_CHECK();
+        }
+        return COMBAT_OK;
+    }
     const int bytes = (5 * hw * hw + 2 * hw) * 4;
     if (set_smem(trigger_pair_bwd_kernel, bytes)) return COMBAT_ELAUNCH;
     COMBAT_LAUNCH(trigger_pair_bwd_kernel, dim3(3, 2 * n), dim3(256), bytes, as_stream(stream), x,
@@ -975,8 +1189,23 @@ extern "C" int combat_trigger_groups_fwd(const float *x, const void *noise, cons
                                          float noise_rate, int32_t n, int32_t hw, int32_t ps, float *out,
                                          float *mse_partial, void *stream) {
     COMBAT_PLAN_HOOK(combat_trigger_groups_fwd, x, noise, P, k1, noise_rate, n, hw, ps, out, mse_partial);
-    if (!x || !noise || !P || !k1 || !out || n < 0 || ps < 1 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (!x || !noise || !P || !k1 || !out || n < 0 || ps < 1 || hw < 16 || hw > 256 || (hw & 3) || (hw > 64 && (hw & 15))) return COMBAT_EINVAL;
     if (n == 0) return COMBAT_OK;
+    if (hw > 64) {      // strips, as combat_trigger_fwd
+        hipStream_t st = as_stream(stream);
+        if (mse_partial) {
+            hipLaunchKernelGGL(trigger_big_groups_fwd_kernel, dim3(hw / 16, 3, n), dim3(256), 18 * hw * 4, st, x,
+                               reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, ps, out);
+            CB_LAUNCH_CHECK();
+            COMBAT_LAUNCH(trigger_big_mse_kernel, dim3(3, n), dim3(1024), 0, st, x, (const float *)out, hw,
+                          (const int *)nullptr, mse_partial);
+        } else {
+            COMBAT_LAUNCH(trigger_big_groups_fwd_kernel, dim3(hw / 16, 3, n), dim3(256), 18 * hw * 4, st, x,
+                          reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, ps, out);
+        }
+        CB_LAUNCH_CHECK();
+        return COMBAT_OK;
+    }
     const int bytes = (4 * hw * hw + 2 * hw) * 4;
     if (set_smem(trigger_groups_fwd_kernel, bytes)) return COMBAT_ELAUNCH;
     COMBAT_LAUNCH(trigger_groups_fwd_kernel, dim3(3, n), dim3(256), bytes, as_stream(stream), x,
@@ -991,9 +1220,35 @@ extern "C" int combat_trigger_groups_bwd(const float *x, const void *noise, cons
                                          void *d_noise, void *stream) {
     COMBAT_PLAN_HOOK(combat_trigger_groups_bwd, x, noise, P, k1, noise_rate, n, hw, ps, d_out, d_out2, out, l2_scale, pre_tanh,
                      d_noise);
-    if (!x || !noise || !P || !k1 || !d_noise || n < 0 || ps < 1 || hw < 16 || hw > 64 || (hw & 3)) return COMBAT_EINVAL;
+    if (!x || !noise || !P || !k1 || !d_noise || n < 0 || ps < 1 || hw < 16 || hw > 256 || (hw & 3) || (hw > 64 && (hw & 15))) return COMBAT_EINVAL;
     if (l2_scale != 0.f && !out) return COMBAT_EINVAL;
     if (n == 0) return COMBAT_OK;
+    if (hw > 64) {
+        // as combat_trigger_bwd: runs of images whose clamp mask fits this stream's scratch, one pair of launches each.
+        // The mask does not depend on the blur, so its kernel is the plain one on the run's images; the second launch
+        // takes the call's own pointers and the run's first image, which its choice of k1 counts from.
+        hipStream_t st = as_stream(stream);
+        const BigRuns rn = big_runs(stream, hw, (size_t)n);
+        if (!rn.mask) return COMBAT_ELAUNCH;
+        const size_t plane = (size_t)hw * hw;
+        const __bf16 *nz = reinterpret_cast<const __bf16 *>(noise);
+        for (int i0 = 0; i0 < n; i0 += rn.run) {
+            const int ni = n - i0 < rn.run ? n - i0 : rn.run;
+            hipLaunchKernelGGL(trigger_big_mask_kernel, dim3(hw / 16, 3, ni), dim3(256), 16 * hw * 4, st,
+                               x + (size_t)i0 * 3 * plane, nz + (size_t)i0 * plane * 8, P, noise_rate, hw, rn.mask);
+            CB_LAUNCH_CHECK();
+            if (i0 + ni < n)
+                hipLaunchKernelGGL(trigger_big_groups_bwd_kernel, dim3(hw / 16, 3, ni), dim3(256), 16 * hw * 4, st, x, nz, P, k1,
+                                   noise_rate, hw, ps, i0, d_out, d_out2, out, l2_scale, pre_tanh,
+                                   (const unsigned short *)rn.mask, reinterpret_cast<__bf16 *>(d_noise));
+            else
+                COMBAT_LAUNCH(trigger_big_groups_bwd_kernel, dim3(hw / 16, 3, ni), dim3(256), 16 * hw * 4, st, x, nz, P, k1,
+                              noise_rate, hw, ps, i0, d_out, d_out2, out, l2_scale, pre_tanh,
+                              (const unsigned short *)rn.mask, reinterpret_cast<__bf16 *>(d_noise));
+            CB_LAUNCH_CHECK();
+        }
+        return COMBAT_OK;
+    }
     const int bytes = (5 * hw * hw + 2 * hw) * 4;
     if (set_smem(trigger_groups_bwd_kernel, bytes)) return COMBAT_ELAUNCH;
     COMBAT_LAUNCH(trigger_groups_bwd_kernel, dim3(3, n), dim3(256), bytes, as_stream(stream), x,

@@ -410,8 +410,8 @@ int combat_unet_up_fused(const void *y, const float *partials, int32_t rows_per_
  * hw: 16 .. 64 in steps of 4 (one workgroup per plane, everything in LDS), or 80 .. 256 in steps of 16 (ImageNet-10's
  * 224: one workgroup per 16-row strip of a plane; P must be symmetric there, as oracle.lowpass_matrix is; mse_partial
  * comes from a second launch of the same call, the backward's clamp mask -- one bit per pixel -- passes through the
- * library's per-stream scratch between its two launches).  Anything else: COMBAT_EINVAL.  The _pair, _groups and _tv
- * variants below take hw <= 64 only.
+ * library's per-stream scratch between its two launches).  Anything else: COMBAT_EINVAL.  The _pair and _groups
+ * variants below follow the same size rule; the _tv variants take hw <= 64 only.
  * ------------------------------------------------------------------------------------------ */
 int combat_trigger_fwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
                        int32_t n, int32_t hw, const int32_t *src_index /* NULL, or output image i is made from row
@@ -428,7 +428,12 @@ int combat_trigger_bwd(const float *x, const void *noise, const float *P, const 
  * Backward, one launch over the 2n rows of d_noise: rows [0, n) get what combat_trigger_bwd(d_bd, d_bd2, out_bd,
  * l2_scale) writes, rows [n, 2n) what combat_trigger_bwd(d_cross) writes (no L2 term: the reference's MSELoss reads
  * inputs_bd only, :250).  Per image the arithmetic of the single-noise entry points, in the same order: the results
- * are bit-identical to two calls of them. */
+ * are bit-identical to two calls of them.
+ * hw: the size rule of combat_trigger_fwd / _bwd.  On the strip route (80 .. 256 in steps of 16) the forward is one
+ * launch over the 2n rows, plus the ordered squared-error launch over out_bd when mse_partial is given; the backward
+ * is a mask launch and a gradient launch per run of rows whose clamp mask (3 hw^2 / 8 bytes per row, 2n rows) fits the
+ * stream's 2 MB scratch: one run up to 111 rows at 224, runs of 85 rows at 256.  A run may straddle the two halves.
+ * n == 0: COMBAT_OK, nothing launched.  l2_scale != 0 without out_bd: COMBAT_EINVAL. */
 int combat_trigger_pair_fwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
                             int32_t n, int32_t hw, float *out_bd, float *out_cross, float *mse_partial, void *stream);
 int combat_trigger_pair_bwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
@@ -441,7 +446,9 @@ int combat_trigger_pair_bwd(const float *x, const void *noise, const float *P, c
  * combat_trigger_fwd / combat_trigger_bwd (without src_index / out_c8) with k1 fp32 [ceil(n / ps)][3]: image i is blurred
  * with k1[i / ps]; the last group may be short.  Per image the arithmetic of the single-kernel entry points, in the same
  * order: out, mse_partial and d_noise are bit-identical to one call of them per chunk.  COMBAT_EINVAL as for
- * combat_trigger_fwd / _bwd, and for ps < 1. */
+ * combat_trigger_fwd / _bwd (their size rule included: 16 .. 64 in steps of 4, or 80 .. 256 in steps of 16 on the strip
+ * route, where the backward is a mask launch and a gradient launch per run of images whose clamp mask fits the stream's
+ * scratch, 3 hw^2 / 8 bytes per image), and for ps < 1.  n == 0: COMBAT_OK, nothing launched. */
 int combat_trigger_groups_fwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
                               int32_t n, int32_t hw, int32_t ps, float *out, float *mse_partial, void *stream);
 int combat_trigger_groups_bwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,

@@ -82,7 +82,10 @@ int main() {
     expect(tf(x, noise, P, k1, 1, 32, -3, out), E, "groups fwd ps < 0");
     expect(tf(x, noise, P, k1, 1, 12, 2, out), E, "groups fwd hw 12");
     expect(tf(x, noise, P, k1, 1, 34, 2, out), E, "groups fwd hw 34");
-    expect(tf(x, noise, P, k1, 1, 128, 2, out), E, "groups fwd hw 128");
+    expect(tf(x, noise, P, k1, 1, 72, 2, out), E, "groups fwd hw 72 (strip route, not a multiple of 16)");
+    expect(tf(x, noise, P, k1, 1, 272, 2, out), E, "groups fwd hw 272");
+    expect(tf(x, noise, P, k1, 0, 224, 2, out), COMBAT_OK, "groups fwd n == 0 at 224");
+    expect(tf(x, noise, P, k1, 1, 224, 0, out), E, "groups fwd ps 0 at 224");
     expect(tf(x, noise, P, k1, -1, 32, 2, out), E, "groups fwd n < 0");
     expect(tf(nullptr, noise, P, k1, 1, 32, 2, out), E, "groups fwd NULL x");
     expect(tf(x, nullptr, P, k1, 1, 32, 2, out), E, "groups fwd NULL noise");
@@ -96,6 +99,10 @@ int main() {
     expect(tb(x, k1, 0, 32, 2, out, 0.5f, dn), COMBAT_OK, "groups bwd n == 0");
     expect(tb(x, k1, 1, 32, 0, out, 0.5f, dn), E, "groups bwd ps 0");
     expect(tb(x, k1, 1, 8, 2, out, 0.5f, dn), E, "groups bwd hw 8");
+    expect(tb(x, k1, 1, 72, 2, out, 0.5f, dn), E, "groups bwd hw 72");
+    expect(tb(x, k1, 1, 272, 2, out, 0.5f, dn), E, "groups bwd hw 272");
+    expect(tb(x, k1, 0, 224, 2, out, 0.5f, dn), COMBAT_OK, "groups bwd n == 0 at 224");
+    expect(tb(x, k1, 1, 224, 2, nullptr, 0.5f, dn), E, "groups bwd L2 term without out at 224");
     expect(tb(x, k1, 1, 32, 2, nullptr, 0.5f, dn), E, "groups bwd L2 term without out");
     expect(tb(nullptr, k1, 1, 32, 2, out, 0.5f, dn), E, "groups bwd NULL x");
     expect(tb(x, nullptr, 1, 32, 2, out, 0.5f, dn), E, "groups bwd NULL k1");

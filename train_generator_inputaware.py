@@ -15,6 +15,11 @@ train_generator.py's.  What differs, and is added here:
     --continue_training (:597-618).
 The per-batch body (:170-290) runs as ``combat_amd.step.InputAwareStep`` on the HIP kernels.
 
+--dataset cifar10 | celeba | imagenet10 (reference :100-103, :523-528).  imagenet10: 224 x 224, 10 classes,
+ResNet18(input_size=224), bs forced to 32 (the generator and netC's differentiated pass run over 64 images); the paired
+trigger runs as 16-row strips; no detector checkpoint ships, so pass --allow_missing_F, as for
+train_generator.py.
+
 Data parallel: ``python -m torch.distributed.run --nproc-per-node N ...`` shards BOTH train loaders like the first
 (combat_amd.dist).  Run with two ranks on one GPU over gloo (COMBAT_DIST_BACKEND=gloo: tests/test_inputaware_gpu.py);
 not run over RCCL on several GPUs.

@@ -18,6 +18,10 @@ train_generator.py's.  What differs, and is implemented here:
 The reference's F-model table (:19-28) names detectors this repository has no engine for: every --F_model other than
 'original' / 'original_holdout' is refused.  Its dataloader is train_generator.py's (utils.dataloader).
 
+--dataset cifar10 | celeba | imagenet10 (reference :97-100, :469-): at ImageNet-10's 224 x 224 (10 classes,
+ResNet18(input_size=224), bs forced to 32: eight chunks of four images) the grouped trigger runs as 16-row strips and the
+label conditioning on a 224 x 224 map; pass --allow_missing_F there, as for train_generator.py.
+
 Single process only: MultiLabelStep has no data-parallel path and refuses a process group of more than one rank.
 """
 import torch

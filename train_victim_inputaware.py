@@ -9,6 +9,7 @@ delegate to train_victim.py:
     counted on the non-target-class rows and divided by their number; the info string gains
     "Cross Acc: ... - Best: ..." and the checkpoint the key best_cross_acc.
 The checkpoint lives under ``<saving_prefix>_clean/`` (:289-291).
+--dataset cifar10 | celeba | imagenet10 (224 x 224, bs 32), as train_generator_inputaware.py.
 """
 import os
 
