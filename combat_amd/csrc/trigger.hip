@@ -401,6 +401,8 @@ struct StripRow {
     const float *g1, *g2;        // backward: channel c's planes of its gradients (either may be null)
     const float *op;             // backward: channel c's plane of its output, null without the L2 term
     float l2_scale;
+    const float *tvo;            // backward with the total-variation term: channel c's plane of its output (the stencil's)
+    float tv_scale;
     unsigned short *mask;        // backward: its clamp-mask plane in the scratch, [hw / 16][hw]
     __bf16 *dn;                  // backward: its gradient pixels (c8)
 };
@@ -528,6 +530,47 @@ __global__ __launch_bounds__(1024) void trigger_big_mse_kernel(const float *__re
     }
 }
 
+// The imperceptible step's reduction behind trigger_big_fwd_kernel (train_generator_imperceptible.py:228): the plane's
+// total variation tv[3 img + c] = sum |out[y+1][x] - out[y][x]| + sum |out[y][x+1] - out[y][x]|, and with `mse` the squared
+// error of trigger_big_mse_kernel -- the same subtraction and fma per pixel, the same order, so the same bits.  The TV
+// sum is ordered likewise: a thread adds its pixels in index order (vertical term, then horizontal term), the lanes are
+// folded by shuffles, the sixteen wave sums added in wave order.  The neighbours are read from global memory: a strip
+// kernel never holds the row below its last one.  Neither neighbour leaves the plane (y + 1 < hw, x + 1 < hw).
+__global__ __launch_bounds__(1024) void trigger_big_tv_kernel(const float *__restrict__ x, const float *__restrict__ out, int hw,
+                                                              float *__restrict__ mse, float *__restrict__ tv) {
+    __shared__ float ws[16], wt[16];
+    const int hw2 = hw * hw, tid = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
+    const float *xi = x + ((long)img * 3 + c) * hw2, *oi = out + ((long)img * 3 + c) * hw2;
+    float se = 0.f, tvs = 0.f;
+#pragma unroll 7
+    for (int o = tid; o < hw2; o += 1024) {
+        const float v = oi[o];
+        const float d = v - xi[o];
+        se = fmaf(d, d, se);
+        const int y = o / hw, xx = o - y * hw;
+        if (y + 1 < hw) tvs += fabsf(oi[o + hw] - v);
+        if (xx + 1 < hw) tvs += fabsf(oi[o + 1] - v);
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        se += __shfl_down(se, d, 64);
+        tvs += __shfl_down(tvs, d, 64);
+    }
+    if ((tid & 63) == 0) {
+        ws[tid >> 6] = se;
+        wt[tid >> 6] = tvs;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float t = ws[0], u = wt[0];
+        for (int w = 1; w < 16; ++w) {
+            t += ws[w];
+            u += wt[w];
+        }
+        if (mse) mse[img * 3 + c] = t;
+        tv[img * 3 + c] = u;
+    }
+}
+
 // Backward, first launch: the clamp mask.  P * noise * P is recomputed (as trigger_bwd_kernel does), strip by strip, and
 // only whether x + rate * (...) lies inside [-1, 1] is kept: bit r of mask[((3 row + c) * hw / 16 + strip) * hw + j] is
 // pixel (16 strip + r, j) of the launch's row `row` (grid z).  hw^2 / 8 bytes per plane.  LDS: Ts [16][hw].
@@ -581,6 +624,11 @@ __global__ __launch_bounds__(256) void trigger_big_pair_mask_kernel(const float 
 // 2 l2 (out - x).  W is never stored: thread j walks down column j and forms W[k][j] from the mask bit and the 3 x 3
 // blur adjoint of g, whose three row terms (g Kb)[k - 1 .. k + 1][j] slide along in registers (one new row of three
 // pixels per k).  LDS: Ts [16][hw].
+// TV (the imperceptible step, train_generator_imperceptible.py:228, :234-237): g gains tv_scale * the sign stencil of
+// trigger_bwd_plane<true>, in its order and with its sgnf.  The stencil's neighbours of `out` (w.tvo) come from global
+// memory: out is complete before the backward starts, so they cross the strips' seams freely; the guards on the row a and
+// the column b keep them inside the plane.  Without TV the body is the one it was.
+template <bool TV>
 __device__ __forceinline__ void trigger_big_bwd_strip(float *sm, const float *__restrict__ P, float rate, int hw, int r0, int c,
                                                       int pre_tanh, const StripRow &w) {
     const int tid = threadIdx.x;
@@ -594,17 +642,29 @@ __device__ __forceinline__ void trigger_big_bwd_strip(float *sm, const float *__
     const int jm = j > 0 ? j - 1 : j, jp = j + 1 < hw ? j + 1 : j;
     const float cm = j > 0 ? blur_coef(kk, hw, j - 1, j) : 0.f, c0 = blur_coef(kk, hw, j, j),
                 cp = j + 1 < hw ? blur_coef(kk, hw, j + 1, j) : 0.f;
-    auto g_at = [&](int o) {
+    const float *tvo = w.tvo;
+    const float tv_scale = w.tv_scale;
+    auto g_at = [&](int a, int b) {
+        const int o = a * hw + b;
         float g = g1 ? g1[o] : 0.f;
         if (g2) g += g2[o];
         if (op) g = fmaf(2.f * l2_scale, op[o] - xi[o], g);
+        if (TV) {
+            const float v = tvo[o];
+            float s = 0.f;
+            if (a > 0) s += sgnf(v - tvo[o - hw]);
+            if (a + 1 < hw) s -= sgnf(tvo[o + hw] - v);
+            if (b > 0) s += sgnf(v - tvo[o - 1]);
+            if (b + 1 < hw) s -= sgnf(tvo[o + 1] - v);
+            g = fmaf(tv_scale, s, g);
+        }
         return g;
     };
     auto h_row = [&](int a) {
         float s = 0.f;
-        if (j > 0) s = fmaf(cm, g_at(a * hw + jm), s);
-        s = fmaf(c0, g_at(a * hw + j), s);
-        if (j + 1 < hw) s = fmaf(cp, g_at(a * hw + jp), s);
+        if (j > 0) s = fmaf(cm, g_at(a, jm), s);
+        s = fmaf(c0, g_at(a, j), s);
+        if (j + 1 < hw) s = fmaf(cp, g_at(a, jp), s);
         return s;
     };
     float hm = 0.f, h0 = h_row(0), hp = h_row(1);
@@ -665,7 +725,35 @@ __global__ __launch_bounds__(256) void trigger_big_bwd_kernel(const float *__res
     w.l2_scale = l2_scale;
     w.mask = const_cast<unsigned short *>(mask) + ((long)img * 3 + c) * (hw >> 4) * hw;
     w.dn = d_noise + (long)img * hw2 * 8;
-    trigger_big_bwd_strip(sm, P, rate, hw, blockIdx.x * 16, c, pre_tanh, w);
+    trigger_big_bwd_strip<false>(sm, P, rate, hw, blockIdx.x * 16, c, pre_tanh, w);
+}
+
+// trigger_big_bwd_kernel + tv_scale * d TV(out) / d out in the image gradient (trigger_tv_bwd_kernel on strips; outp is
+// required, whatever l2_scale is).
+__global__ __launch_bounds__(256) void trigger_big_tv_bwd_kernel(const float *__restrict__ x, const __bf16 *__restrict__ noise,
+                                                                 const float *__restrict__ P, const float *__restrict__ k1,
+                                                                 float rate, int hw, const float *__restrict__ d_out,
+                                                                 const float *__restrict__ d_out2,
+                                                                 const float *__restrict__ outp, float l2_scale,
+                                                                 float tv_scale, int pre_tanh,
+                                                                 const unsigned short *__restrict__ mask,
+                                                                 __bf16 *__restrict__ d_noise) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int hw2 = hw * hw, c = blockIdx.y, img = blockIdx.z;
+    const long pl = ((long)img * 3 + c) * hw2;
+    StripRow w = {};
+    w.xi = x + pl;
+    w.nz = noise + (long)img * hw2 * 8;
+    w.k1 = k1;
+    w.g1 = d_out ? d_out + pl : nullptr;
+    w.g2 = d_out2 ? d_out2 + pl : nullptr;
+    w.op = l2_scale != 0.f ? outp + pl : nullptr;
+    w.l2_scale = l2_scale;
+    w.tvo = outp + pl;
+    w.tv_scale = tv_scale;
+    w.mask = const_cast<unsigned short *>(mask) + ((long)img * 3 + c) * (hw >> 4) * hw;
+    w.dn = d_noise + (long)img * hw2 * 8;
+    trigger_big_bwd_strip<true>(sm, P, rate, hw, blockIdx.x * 16, c, pre_tanh, w);
 }
 
 // Rows row0 .. row0 + gridDim.z - 1 of the paired backward (trigger_pair_bwd_kernel on strips), behind
@@ -694,7 +782,7 @@ __global__ __launch_bounds__(256) void trigger_big_pair_bwd_kernel(const float *
     w.op = w.l2_scale != 0.f ? out_bd + pl : nullptr;
     w.mask = const_cast<unsigned short *>(mask) + ((long)blockIdx.z * 3 + c) * (hw >> 4) * hw;
     w.dn = d_noise + (long)row * hw2 * 8;
-    trigger_big_bwd_strip(sm, P, rate, hw, blockIdx.x * 16, c, pre_tanh, w);
+    trigger_big_bwd_strip<false>(sm, P, rate, hw, blockIdx.x * 16, c, pre_tanh, w);
 }
 
 // Images img0 .. img0 + gridDim.z - 1 of the grouped backward (trigger_groups_bwd_kernel on strips), behind
@@ -720,7 +808,7 @@ __global__ __launch_bounds__(256) void trigger_big_groups_bwd_kernel(const float
     w.l2_scale = l2_scale;
     w.mask = const_cast<unsigned short *>(mask) + ((long)blockIdx.z * 3 + c) * (hw >> 4) * hw;
     w.dn = d_noise + (long)img * hw2 * 8;
-    trigger_big_bwd_strip(sm, P, rate, hw, blockIdx.x * 16, c, pre_tanh, w);
+    trigger_big_bwd_strip<false>(sm, P, rate, hw, blockIdx.x * 16, c, pre_tanh, w);
 }
 
 // ------------------------------------------------------------------ augmentation
@@ -1109,6 +1197,65 @@ extern "C" int combat_trigger_tv_bwd(const float *x, const void *noise, const fl
                        reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, d_out, d_out2, out, l2_scale,
                        tv_scale, pre_tanh, reinterpret_cast<__bf16 *>(d_noise));
     CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+
+// The total-variation trigger on the strip route (80 <= hw <= 256, hw % 16 == 0; smaller planes belong to
+// combat_trigger_tv_fwd / _bwd).  Forward: trigger_big_fwd_kernel as combat_trigger_fwd launches it, then one reduction
+// over the finished planes for the squared-error and total-variation partials.
+extern "C" int combat_trigger_tv_big_fwd(const float *x, const void *noise, const float *P, const float *k1,
+                                         float noise_rate, int32_t n, int32_t hw, float *out, float *mse_partial,
+                                         float *tv_partial, void *stream) {
+    COMBAT_PLAN_HOOK(combat_trigger_tv_big_fwd, x, noise, P, k1, noise_rate, n, hw, out, mse_partial, tv_partial);
+    if (!x || !noise || !P || !k1 || !out || !tv_partial || n < 0 || hw < 80 || hw > 256 || (hw & 15)) return COMBAT_EINVAL;
+    if (n == 0) return COMBAT_OK;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(trigger_big_fwd_kernel, dim3(hw / 16, 3, n), dim3(256), 18 * hw * 4, st, x,
+                       reinterpret_cast<const __bf16 *>(noise), P, k1, noise_rate, hw, (const int *)nullptr, out,
+                       (__bf16 *)nullptr);
+    CB_LAUNCH_CHECK();
+    COMBAT_LAUNCH(trigger_big_tv_kernel, dim3(3, n), dim3(1024), 0, st, x, (const float *)out, hw, mse_partial, tv_partial);
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+
+// Backward: combat_trigger_bwd's runs of images (mask launch, gradient launch), the gradient launch with the stencil.
+extern "C" int combat_trigger_tv_big_bwd(const float *x, const void *noise, const float *P, const float *k1,
+                                         float noise_rate, int32_t n, int32_t hw, const float *d_out, const float *d_out2,
+                                         const float *out, float l2_scale, float tv_scale, int32_t pre_tanh, void *d_noise,
+                                         void *stream) {
+    if (hw < 80 || hw > 256 || (hw & 15)) return COMBAT_EINVAL;
+    if (tv_scale == 0.f)      // nothing to add: the launches of combat_trigger_bwd itself
+        return combat_trigger_bwd(x, noise, P, k1, noise_rate, n, hw, d_out, d_out2, out, l2_scale, pre_tanh, d_noise, stream);
+    COMBAT_PLAN_HOOK(combat_trigger_tv_big_bwd, x, noise, P, k1, noise_rate, n, hw, d_out, d_out2, out, l2_scale, tv_scale,
+                     pre_tanh, d_noise);
+    if (!x || !noise || !P || !k1 || !out || !d_noise || n < 0) return COMBAT_EINVAL;
+    if (n == 0) return COMBAT_OK;
+    hipStream_t st = as_stream(stream);
+    const size_t plane = (size_t)hw * hw;
+    const BigRuns rn = big_runs(stream, hw, (size_t)n);
+    unsigned short *mask = rn.mask;
+    const int run = rn.run;
+    if (!mask) return COMBAT_ELAUNCH;
+    for (int i0 = 0; i0 < n; i0 += run) {
+        const int ni = n - i0 < run ? n - i0 : run;
+        const size_t o3 = (size_t)i0 * 3 * plane, o8 = (size_t)i0 * plane * 8;
+        const __bf16 *nz = reinterpret_cast<const __bf16 *>(noise) + o8;
+        hipLaunchKernelGGL(trigger_big_mask_kernel, dim3(hw / 16, 3, ni), dim3(256), 16 * hw * 4, st, x + o3, nz, P,
+                           noise_rate, hw, mask);
+        CB_LAUNCH_CHECK();
+        if (i0 + ni < n)
+            hipLaunchKernelGGL(trigger_big_tv_bwd_kernel, dim3(hw / 16, 3, ni), dim3(256), 16 * hw * 4, st, x + o3, nz, P, k1,
+                               noise_rate, hw, d_out ? d_out + o3 : nullptr, d_out2 ? d_out2 + o3 : nullptr, out + o3,
+                               l2_scale, tv_scale, pre_tanh, (const unsigned short *)mask,
+                               reinterpret_cast<__bf16 *>(d_noise) + o8);
+        else
+            COMBAT_LAUNCH(trigger_big_tv_bwd_kernel, dim3(hw / 16, 3, ni), dim3(256), 16 * hw * 4, st, x + o3, nz, P, k1,
+                          noise_rate, hw, d_out ? d_out + o3 : nullptr, d_out2 ? d_out2 + o3 : nullptr, out + o3,
+                          l2_scale, tv_scale, pre_tanh, (const unsigned short *)mask,
+                          reinterpret_cast<__bf16 *>(d_noise) + o8);
+        CB_LAUNCH_CHECK();
+    }
     return COMBAT_OK;
 }
 

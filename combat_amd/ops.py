@@ -286,21 +286,24 @@ def trigger_bwd(x, noise, p_mat, k1, noise_rate, d_out, out, l2_scale, d_noise, 
 
 
 def trigger_tv_fwd(x, noise, p_mat, k1, noise_rate, out, tv_partial, mse_partial=None) -> None:
-    """trigger_fwd + tv_partial (fp32 [3n]): the per-(image, channel) total variation of `out`."""
+    """trigger_fwd + tv_partial (fp32 [3n]): the per-(image, channel) total variation of `out`.  hw > 64: the strip
+    route's entry point."""
     n, _, hw, _ = x.shape
-    check(lib.combat_trigger_tv_fwd(x.data_ptr(), noise.data_ptr(), p_mat.data_ptr(), k1.data_ptr(), noise_rate, n, hw,
-                                    out.data_ptr(), _p(mse_partial), tv_partial.data_ptr(), _stream()),
-          "combat_trigger_tv_fwd", str(tuple(x.shape)))
+    name = "combat_trigger_tv_big_fwd" if hw > 64 else "combat_trigger_tv_fwd"
+    check(getattr(lib, name)(x.data_ptr(), noise.data_ptr(), p_mat.data_ptr(), k1.data_ptr(), noise_rate, n, hw,
+                             out.data_ptr(), _p(mse_partial), tv_partial.data_ptr(), _stream()),
+          name, str(tuple(x.shape)))
 
 
 def trigger_tv_bwd(x, noise, p_mat, k1, noise_rate, d_out, out, l2_scale, tv_scale, d_noise, pre_tanh=False,
                    d_out2=None) -> None:
     """trigger_bwd with tv_scale * (sign stencil of `out`) added to the image gradient before the blur adjoint."""
     n, _, hw, _ = x.shape
-    check(lib.combat_trigger_tv_bwd(x.data_ptr(), noise.data_ptr(), p_mat.data_ptr(), k1.data_ptr(), noise_rate, n, hw,
-                                    _p(d_out), _p(d_out2), _p(out), l2_scale, tv_scale, int(pre_tanh), d_noise.data_ptr(),
-                                    _stream()),
-          "combat_trigger_tv_bwd", str(tuple(x.shape)))
+    name = "combat_trigger_tv_big_bwd" if hw > 64 else "combat_trigger_tv_bwd"
+    check(getattr(lib, name)(x.data_ptr(), noise.data_ptr(), p_mat.data_ptr(), k1.data_ptr(), noise_rate, n, hw,
+                             _p(d_out), _p(d_out2), _p(out), l2_scale, tv_scale, int(pre_tanh), d_noise.data_ptr(),
+                             _stream()),
+          name, str(tuple(x.shape)))
 
 
 def trigger_pair_fwd(x, noise, p_mat, k1, noise_rate, out_bd, out_cross, mse_partial=None) -> None:

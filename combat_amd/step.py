@@ -1016,7 +1016,10 @@ class ImperceptibleStep(AlternatedStep):
     trigger backward launch, and the logged sum rides in the log-terms launch: the step's launch count is the parent's.
     Phase C, the draws' order and the networks are the parent's; like the input-aware script, the reference blurs with
     the module-level T.GaussianBlur(kernel_size=3, sigma=(0.1, 1)) (:52), whatever --kernel_size / --sigma say.  At
-    tv_weight 0 the trigger backward is the parent's launch, and the step leaves the parent's bits."""
+    tv_weight 0 the trigger backward is the parent's launch, and the step leaves the parent's bits.  Images larger
+    than 64 pixels (ImageNet-10's 224 x 224) take combat_trigger_tv_big_fwd / _bwd, the strip route: the sums come from
+    the reduction launch behind the strip forward (where the parent has its squared-error launch), the stencil reads
+    inputs_bd across the strips' seams; the launch count is the parent's there too."""
 
     FIXED_BLUR = True    # (the draws keep the parent's order: one sigma per create_inputs_bd call, :172-174 and :203)
     CAN_MERGE_C = False
@@ -1029,9 +1032,9 @@ class ImperceptibleStep(AlternatedStep):
     def _trigger_g(self, x_ptr, n, k1g, s2) -> None:
         """inputs_bd of the whole batch (:203) with its squared-error and total-variation partials."""
         s = self.cur
-        ops.check(lib.combat_trigger_tv_fwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g,
-                                            float(self.opt.noise_rate), n, self.hw, s.bd.data_ptr(), s.mse.data_ptr(),
-                                            s.tv.data_ptr(), s2), "trigger tv G")
+        fwd = lib.combat_trigger_tv_big_fwd if self.hw > 64 else lib.combat_trigger_tv_fwd      # strips / whole planes
+        ops.check(fwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g, float(self.opt.noise_rate), n,
+                      self.hw, s.bd.data_ptr(), s.mse.data_ptr(), s.tv.data_ptr(), s2), "trigger tv G")
 
     def _log_terms(self, n, s2, f_logits) -> None:
         """The parent's logged terms + loss_tv (:228, :245) -> acc[2]."""
@@ -1045,10 +1048,10 @@ class ImperceptibleStep(AlternatedStep):
         s, hw = self.cur, self.hw
         l2_scale = float(self.opt.L2_weight) / float(n * 3 * hw * hw)
         tv_scale = float(self.opt.tv_weight) / float(n)                        # .mean() over the batch (:228)
-        ops.check(lib.combat_trigger_tv_bwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g,
-                                            float(self.opt.noise_rate), n, hw, s.d_bd.data_ptr(), s.d_bd2.data_ptr(),
-                                            s.bd.data_ptr(), l2_scale, tv_scale, 1,
-                                            s.sG.buf("g.z", (n, hw, hw, 8)).data_ptr(), st), "trigger tv bwd")
+        bwd = lib.combat_trigger_tv_big_bwd if hw > 64 else lib.combat_trigger_tv_bwd
+        ops.check(bwd(x_ptr, self.eG.output(s.sG).data_ptr(), self.P.data_ptr(), k1g, float(self.opt.noise_rate), n, hw,
+                      s.d_bd.data_ptr(), s.d_bd2.data_ptr(), s.bd.data_ptr(), l2_scale, tv_scale, 1,
+                      s.sG.buf("g.z", (n, hw, hw, 8)).data_ptr(), st), "trigger tv bwd")
         self._backward_allreduce(s.pl["G_b"], self.eG, prof)
 
     def read_metrics(self, reset: bool = False) -> Dict[str, float]:

@@ -517,6 +517,26 @@ int combat_trigger_tv_bwd(const float *x, const void *noise, const float *P, con
                           const float *out, float l2_scale, float tv_scale, int32_t pre_tanh, void *d_noise,
                           void *stream);
 
+/* The same trigger on planes too large for one workgroup's LDS (ImageNet-10's 224 x 224;
+ * train_generator_imperceptible.py:228, :234-237 with the imagenet10 branch of :94, :469): hw in 80 .. 256 and a multiple
+ * of 16, the strip route of combat_trigger_fwd / _bwd.  Any other hw (hw <= 64 belongs to the two entry points above),
+ * n < 0 or a NULL x / noise / P / k1 / out / tv_partial / d_noise is COMBAT_EINVAL with nothing launched; n == 0 is
+ * COMBAT_OK.
+ * combat_trigger_tv_big_fwd: the strip launch of combat_trigger_fwd (out carries its bits), then one reduction launch
+ * over the finished planes: tv_partial fp32 [3n] as above and, if mse_partial != NULL, combat_trigger_fwd's mse_partial
+ * bits.  Both sums are ordered (no atomics): the same bits every run, in both deterministic modes.
+ * combat_trigger_tv_big_bwd: the launches of combat_trigger_bwd's strip route with the stencil above joined to the image
+ * gradient by one fma, g = fma(tv_scale, stencil, d_out (+ d_out2) (+ the L2 term)); the stencil reads `out` across the
+ * strips' seams, never across a plane's border.  tv_scale == 0 is combat_trigger_bwd itself (bit-identical; `out` is
+ * then needed only for the L2 term). */
+int combat_trigger_tv_big_fwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
+                              int32_t n, int32_t hw, float *out, float *mse_partial /* may be NULL */,
+                              float *tv_partial, void *stream);
+int combat_trigger_tv_big_bwd(const float *x, const void *noise, const float *P, const float *k1, float noise_rate,
+                              int32_t n, int32_t hw, const float *d_out, const float *d_out2 /* NULL, or added to d_out */,
+                              const float *out, float l2_scale, float tv_scale, int32_t pre_tanh, void *d_noise,
+                              void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * PostTensorTransform (utils/dataloader.py:45-60): per-sample crop(pad, integer offset) ->
  * rotation(bilinear, zeros, about the centre) -> horizontal flip, in one gather.
