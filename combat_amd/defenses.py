@@ -603,8 +603,8 @@ class NeuralCleanse:
         plan = self._plans.get(key)
         if plan is None:
             slot, blend, fwd, bwd, update = self._parts(n, target_label, grad_out)
-            for part in (fwd, bwd):     # eval passes: one queue, no marks -- their calls can be re-recorded in line
-                assert not part.aux and not part.after and not part.marks, part.name
+            for part in (fwd, bwd):     # the step is single-queue by design: eval passes, nothing beside the stream, no marks
+                assert all(c.queue is None and c.after is None and c.mark is None for c in part.calls), part.name
             plan = Plan("nc.step.%d.%d" % (n, target_label))
             plan.add("nc.blend", lib.combat_nc_blend, *blend)
             plan.calls += fwd.calls

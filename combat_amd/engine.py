@@ -36,6 +36,19 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+class Call:
+    """One recorded call of a plan, with everything the replay needs to know about it."""
+
+    __slots__ = ("func", "args", "what", "queue", "after", "mark", "wgrad")
+
+    def __init__(self, func, args, what: str, queue: Optional[int] = None, after: Optional["Call"] = None):
+        self.func, self.args, self.what = func, args, what
+        self.queue = queue    # None: the plan's own stream; k: auxiliary queue k (the call may run beside the calls that follow it)
+        self.after = after    # an earlier Call this one waits for (on whatever queue that ran)
+        self.mark = None      # flat-gradient offset that is complete once this call has been enqueued
+        self.wgrad = None     # combat_conv_wgrad: its WgradArgs; combat_conv_wgrad_group: its members', as recorded
+
+
 class Plan:
     """An ordered list of C-ABI calls with pre-marshalled arguments (stream appended at run)."""
 
@@ -60,46 +73,53 @@ class Plan:
 
     def __init__(self, name: str):
         self.name = name
-        self.calls: List[Tuple] = []
+        self.calls: List[Call] = []       # the schedule: queue, dependency, mark and weight-gradient arguments travel with each call
         self._keep: List = []
-        self.marks: Dict[int, int] = {}   # call index -> flat-gradient offset complete after that call
-        self.aux: Dict[int, int] = {}     # call index -> auxiliary queue of the calls that may run beside the plan's own stream
         self.aux_queues = Plan.default_aux_queues   # auxiliary queues the aux calls are dealt to, round-robin (each with its own
         #                                   weight-gradient scratch).  Measured: 2 for the generator's backward 4.19 -> 4.23
         #                                   ms/step, 2 for the surrogate's 4.14 -> 4.17: one queue it stays
-        self.wgrads: List[Tuple] = []     # (call index, WgradArgs) of the weight-gradient launches
         self._ws = None
         self._cplan = None                # combat_plan* of the compiled form (built on first run)
         self._prog = None
-        self.after: Dict[int, int] = {}   # call index -> index of an earlier call it waits for (on whatever queue that ran)
-        self.pending_reduces: List[Tuple] = []   # (what, WgradArgs, index of its weight-gradient call)
+        self.pending_reduces: List[Tuple] = []   # (what, WgradArgs, its weight-gradient Call)
         self.chain: Dict[int, Tuple] = {}        # auxiliary queue -> (what, WgradArgs) of the launch whose slabs await the next one
         self.chain_count: Dict[int, int] = {}    # auxiliary queue -> slab-leaving launches so far (alternates the two regions)
 
-    def add(self, what: str, cfunc, *args, aux: bool = False, after: Optional[int] = None) -> None:
+    def add(self, what: str, cfunc, *args, aux: bool = False, after: Optional[Call] = None) -> Call:
         """aux: the call's result is only consumed after the plan (weight gradients: by the optimiser /
         all-reduce), so it may run on the auxiliary stream beside the calls that follow it.
-        after: index of an earlier call (typically an aux one) this call must wait for."""
-        self.calls.append((cfunc, args, what))
+        after: an earlier call (typically an aux one) this call must wait for."""
+        call = Call(cfunc, args, what, self.next_aux_queue() if aux else None, after)
+        self.calls.append(call)
+        self._changed()
+        return call
+
+    def _changed(self) -> None:       # the call list was edited: the compiled form is rebuilt on the next run
         self._prog = None
-        if aux:
-            self.aux[len(self.calls) - 1] = self.next_aux_queue()
-        if after is not None:
-            self.after[len(self.calls) - 1] = after
+
+    @property
+    def mark_offsets(self) -> List[int]:
+        """The all-reduce marks' flat-gradient offsets, in call order."""
+        return [c.mark for c in self.calls if c.mark is not None]
+
+    @property
+    def wgrads(self) -> List:
+        """Every WgradArgs of the plan in recorded order (the members of a grouped call one by one)."""
+        return [a for c in self.calls if c.wgrad is not None for a in (c.wgrad if isinstance(c.wgrad, list) else [c.wgrad])]
 
     def flush_reduces(self) -> None:
         """Issue the reductions of the weight gradients recorded with defer_reduce so far: on the plan's own stream,
         each waiting for its weight-gradient launch only.  The auxiliary queue then holds a chain of weight-gradient
         kernels instead of (kernel, reduction) pairs -- the reductions were 10 of every 40 us of what is the critical
         path of both training backward passes -- and the reductions run while it works on the next layers."""
-        for what, a, ci in self.pending_reduces:
-            self.add(what, lib.combat_conv_wgrad_reduce, ctypes.byref(a), after=ci)
+        for what, a, call in self.pending_reduces:
+            self.add(what, lib.combat_conv_wgrad_reduce, ctypes.byref(a), after=call)
         self.pending_reduces = []
         self.chain = {}      # (reduce-behind: the chains' last launches were in the list above; the next launch starts a new chain)
 
     def next_aux_queue(self) -> int:
         """Queue the next aux call will be given (round-robin over `aux_queues`)."""
-        return len(self.aux) % self.aux_queues
+        return sum(1 for c in self.calls if c.queue is not None) % self.aux_queues
 
     def hold(self, *objs) -> None:
         self._keep.extend(objs)
@@ -107,11 +127,12 @@ class Plan:
     def merge_convs(self, i: int) -> None:
         """Calls i and i + 1 are two combat_conv_gemm launches with no data dependence between them (a residual
         block's shortcut and its first convolution over the same input): make them ONE combat_conv_gemm_pair call.
-        Only while nothing recorded after them is indexed by position (forward plans: no marks, no aux calls)."""
-        (f0, a0, w0), (f1, a1, w1) = self.calls[i], self.calls[i + 1]
-        assert f0 is lib.combat_conv_gemm and f1 is lib.combat_conv_gemm and not self.marks and not self.aux
-        self.calls[i:i + 2] = [(lib.combat_conv_gemm_pair, (a0[0], a1[0]), w0 + "+" + w1)]
-        self._prog = None
+        Both are plain in-line calls: no queue, no mark, no dependency of or on another call."""
+        two = self.calls[i:i + 2]
+        assert all(c.func is lib.combat_conv_gemm and c.queue is None and c.after is None and c.mark is None for c in two)
+        assert not any(c.after in two for c in self.calls)
+        self.calls[i:i + 2] = [Call(lib.combat_conv_gemm_pair, (two[0].args[0], two[1].args[0]), two[0].what + "+" + two[1].what)]
+        self._changed()
 
     def workspace(self, device) -> torch.Tensor:
         """Scratch of this plan's convolutions (split reductions of skinny layers).  Per plan: the calls of
@@ -124,7 +145,8 @@ class Plan:
         """Every gradient at flat offset >= grad_offset is final once the calls recorded so far ran."""
         if self.flush_at_marks or grad_offset == 0:
             self.flush_reduces()
-        self.marks[len(self.calls) - 1] = grad_offset
+        self.calls[-1].mark = grad_offset
+        self._changed()
 
     compiled = os.environ.get("COMBAT_PLAN_PY", "0") != "1"   # False: replay every plan from Python (debugging / A-B timing)
 
@@ -139,50 +161,43 @@ class Plan:
         cp = self._cplan = lib.combat_plan_create()
         if not cp:
             raise CombatHipError("combat_plan_create failed")
-        prog, names, begin = [], [], None
-        cindex = {}      # plan call index -> index inside the combat_plan
-        for ci, (cfunc, args, what) in enumerate(self.calls):
+        items, names = [], []             # one item per call and per mark; runs of C-ABI calls are joined below
+        cindex: Dict[Call, int] = {}      # call -> its index inside the combat_plan
+        for call in self.calls:
             captured = False
-            if getattr(cfunc, "argtypes", None) is not None:       # a ctypes entry point
-                ops.check(lib.combat_plan_record(cp, self.aux.get(ci, -1)), "combat_plan_record")
+            if getattr(call.func, "argtypes", None) is not None:       # a ctypes entry point
+                ops.check(lib.combat_plan_record(cp, -1 if call.queue is None else call.queue), "combat_plan_record")
                 try:
-                    rc = cfunc(*args, None)
+                    rc = call.func(*call.args, None)
                 finally:
                     captured = not lib.combat_plan_record_cancel()
                 if captured and rc:
-                    raise CombatHipError("%s/%s: recording failed (%d)" % (self.name, what, rc))
+                    raise CombatHipError("%s/%s: recording failed (%d)" % (self.name, call.what, rc))
             if captured:
-                names.append(what)
-                cindex[ci] = len(names) - 1
-                if ci in self.after:
-                    ops.check(lib.combat_plan_set_after(cp, cindex[self.after[ci]]), "combat_plan_set_after")
-                if begin is None:
-                    begin = len(names) - 1
+                cindex[call] = len(names)
+                names.append(call.what)
+                if call.after is not None:
+                    ops.check(lib.combat_plan_set_after(cp, cindex[call.after]), "combat_plan_set_after")
+                items.append(("c", len(names) - 1, len(names)))
             else:
-                if begin is not None:
-                    prog.append(("c", begin, len(names)))
-                    begin = None
-                assert ci not in self.aux and ci not in self.after, "only C-ABI calls can run on an auxiliary queue / wait for a call"
-                prog.append(("py", cfunc, args, what))
-            if ci in self.marks:
-                if begin is not None:
-                    prog.append(("c", begin, len(names)))
-                    begin = None
-                prog.append(("mark", self.marks[ci]))
-        if begin is not None:
-            prog.append(("c", begin, len(names)))
+                assert call.queue is None and call.after is None, "only C-ABI calls can run on an auxiliary queue / wait for a call"
+                items.append(("py", call.func, call.args, call.what))
+            if call.mark is not None:
+                items.append(("mark", call.mark))
         assert lib.combat_plan_size(cp) == len(names)
-        # without an all-reduce callback the marks are no-ops: neighbouring C ranges become one foreign call
-        merged = []
-        for it in prog:
-            if it[0] == "mark":
-                continue
-            if it[0] == "c" and merged and merged[-1][0] == "c" and merged[-1][2] == it[1]:
-                merged[-1] = ("c", merged[-1][1], it[2])
-            else:
-                merged.append(it)
-        self._prog, self._prog_nomark, self._cnames = prog, merged, names
-        return prog
+
+        def ranges(items):                # neighbouring C-ABI calls become one foreign call (no all-reduce callback: the marks drop out first)
+            out = []
+            for it in items:
+                if it[0] == "c" and out and out[-1][0] == "c":
+                    out[-1] = ("c", out[-1][1], it[2])
+                else:
+                    out.append(it)
+            return out
+
+        self._prog, self._prog_nomark, self._cnames = ranges(items), ranges([it for it in items if it[0] != "mark"]), names
+        self._has_aux = any(c.queue is not None for c in self.calls)
+        return self._prog
 
     def run(self, prof: Optional[list] = None, on_mark=None) -> None:
         """Replay.  The launch list is walked in C (combat_plan_run: one foreign call per plan, or per range between
@@ -197,7 +212,7 @@ class Plan:
             prog = self._prog_nomark
         stream = torch.cuda.current_stream()
         st = stream.cuda_stream
-        n_aux = self.aux_queues if (self.aux and not Plan.serial) else 0
+        n_aux = self.aux_queues if (self._has_aux and not Plan.serial) else 0
         auxp = _aux_pointers(stream, n_aux) if n_aux else None
         cp = self._cplan
         for it in prog:
@@ -235,14 +250,16 @@ class Plan:
         stream = torch.cuda.current_stream()
         st = stream.cuda_stream
         auxs = []
-        if self.aux and not Plan.serial:
+        if any(c.queue is not None for c in self.calls) and not Plan.serial:
             auxs = [_aux_stream(stream, k) for k in range(self.aux_queues)]
         used = set()
-        awaited = set(self.after.values()) if auxs else set()
-        done: Dict[int, torch.cuda.Event] = {}
-        for ci, (cfunc, args, what) in enumerate(self.calls):
-            if auxs and ci in self.after and self.after[ci] in done:
-                (auxs[self.aux[ci]] if ci in self.aux else stream).wait_event(done[self.after[ci]])
+        awaited = {c.after for c in self.calls if c.after is not None} if auxs else set()
+        done: Dict[Call, torch.cuda.Event] = {}
+        for call in self.calls:
+            cfunc, args, what = call.func, call.args, call.what
+            own = auxs[call.queue] if auxs and call.queue is not None else stream     # the queue this call belongs to
+            if call.after in done:
+                own.wait_event(done[call.after])
             if prof is not None and cfunc is lib.combat_conv_gemm_pair:     # measured one kernel at a time
                 rc = 0
                 for sub, arg in zip(what.split("+"), args):
@@ -266,32 +283,25 @@ class Plan:
                 rc = cfunc(*args, st)
                 e1.record(stream)
                 prof.append((self.name + "/" + what, args[0]._obj, e0, e1))
-            elif auxs and ci in self.aux:
+            elif own is not stream:
                 # everything enqueued so far (the producers of this call's operands) happens-before it
-                q = self.aux[ci]
-                ev = torch.cuda.Event()
-                ev.record(stream)
-                auxs[q].wait_event(ev)
-                rc = cfunc(*args, auxs[q].cuda_stream)
-                used.add(q)
+                own.wait_stream(stream)
+                rc = cfunc(*args, own.cuda_stream)
+                used.add(call.queue)
             else:
                 rc = cfunc(*args, st)
             if rc:
                 kind = {-1: "invalid shape/argument", -2: "HIP launch failed"}.get(rc, "status %d" % rc)
                 raise CombatHipError("%s/%s: %s" % (self.name, what, kind))
-            if ci in awaited:
-                done[ci] = torch.cuda.Event()
-                done[ci].record(auxs[self.aux[ci]] if ci in self.aux else stream)
-            if on_mark is not None and ci in self.marks:
+            if call in awaited:
+                done[call] = torch.cuda.Event()
+                done[call].record(own)
+            if on_mark is not None and call.mark is not None:
                 for q in used:   # the gradients above the mark include auxiliary-stream results
-                    ev = torch.cuda.Event()
-                    ev.record(auxs[q])
-                    stream.wait_event(ev)
-                on_mark(self.marks[ci])
+                    stream.wait_stream(auxs[q])
+                on_mark(call.mark)
         for q in used:           # join: whoever runs after the plan sees every result
-            ev = torch.cuda.Event()
-            ev.record(auxs[q])
-            stream.wait_event(ev)
+            stream.wait_stream(auxs[q])
 
     def __len__(self):
         return len(self.calls)
@@ -598,10 +608,10 @@ def rec_wgrad(plan: Plan, what: str, src, dy, pc: PackedConv, dw, pro: Optional[
         ws = torch.empty(need, dtype=torch.uint8, device=src.device)
         a.workspace, a.workspace_bytes, a.defer_reduce = ws.data_ptr(), need, 1
     plan.hold(a, src, dy, dw, pro, ws)
-    plan.add(what, lib.combat_conv_wgrad, ctypes.byref(a), aux=aux)
-    plan.wgrads.append((len(plan.calls) - 1, a))
+    call = plan.add(what, lib.combat_conv_wgrad, ctypes.byref(a), aux=aux)
+    call.wgrad = a
     if a.defer_reduce:
-        plan.pending_reduces.append((what + ".reduce", a, len(plan.calls) - 1))
+        plan.pending_reduces.append((what + ".reduce", a, call))
 
 
 def set_deterministic(on: bool) -> None:
@@ -639,13 +649,13 @@ def balance_wgrads(plan: Plan, device) -> None:
     tail = int(os.environ.get("COMBAT_WGRAD_MAIN_TAIL", WGRAD_MAIN_TAIL))
     if tail <= 0 or Plan.serial:
         return
-    aux_calls = [(ci, a) for ci, a in plan.wgrads if ci in plan.aux]
+    aux_calls = [c for c in plan.calls if c.func is lib.combat_conv_wgrad and c.queue is not None]
     ws = _wgrad_workspace(device, -1)
-    plan._prog = None
-    for ci, a in aux_calls[-tail:]:
-        plan.aux.pop(ci, None)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    for c in aux_calls[-tail:]:
+        c.queue = None
+        c.wgrad.workspace, c.wgrad.workspace_bytes = ws.data_ptr(), ws.numel()
         plan.hold(ws)
+    plan._changed()
 
 
 WGRAD_MAIN_TAIL = 0
@@ -680,60 +690,44 @@ def group_wgrads(plan: Plan, device) -> None:
     if mode not in ("tail", "pairs", "stages") or Plan.serial:
         return
     cap = 2 if mode == "pairs" else 4
-    marks = sorted(plan.marks)
-    stage = lambda ci: sum(1 for m in marks if m < ci)
-    args_of = {ci: a for ci, a in plan.wgrads}
-    linked = set(plan.after) | set(plan.after.values())
+    stage, n = {}, 0      # call -> all-reduce marks before it
+    for c in plan.calls:
+        stage[c], n = n, n + (c.mark is not None)
+    linked = {x for c in plan.calls if c.after is not None for x in (c, c.after)}
     PP = ctypes.POINTER(ops.WgradArgs)
 
     def query(members):
-        arr = (PP * len(members))(*[ctypes.pointer(a) for a in members])
+        arr = (PP * len(members))(*[ctypes.pointer(c.wgrad) for c in members])
         return arr, int(lib.combat_conv_wgrad_group_workspace_bytes(arr, len(members)))
 
     runs, run = [], []
-    for ci in sorted(plan.aux):
-        a = args_of.get(ci)
-        ok = a is not None and plan.calls[ci][0] is lib.combat_conv_wgrad and ci not in linked
-        if ok and run and len(run) < cap and plan.aux[run[-1]] == plan.aux[ci] and stage(run[0]) == stage(ci) and \
-                query([args_of[c] for c in run] + [a])[1] >= 0:
-            run.append(ci)
+    for c in (c for c in plan.calls if c.queue is not None):
+        ok = c.func is lib.combat_conv_wgrad and c not in linked
+        if ok and run and len(run) < cap and run[-1].queue == c.queue and stage[run[0]] == stage[c] and query(run + [c])[1] >= 0:
+            run.append(c)
             continue
         if len(run) > 1:
             runs.append(run)
-        run = [ci] if ok and query([a])[1] >= 0 else []
+        run = [c] if ok and query([c])[1] >= 0 else []
     if len(run) > 1:
         runs.append(run)
     if mode == "tail":
         runs = runs[-1:]
     elif mode == "pairs":
-        runs = [r for r in runs if stage(r[0]) == stage(runs[-1][0])]
-    if not runs:
-        return
-    replaced, dropped = {}, set()
+        runs = [r for r in runs if stage[r[0]] == stage[runs[-1][0]]]
+    dropped = {}          # member that leaves the list -> the call of its group
     for r in runs:
-        arr, need = query([args_of[c] for c in r])
-        ws = _wgrad_group_workspace(device, plan.aux[r[-1]], need)
+        arr, need = query(r)
+        last = r[-1]      # becomes the group call: its place, queue and mark stay
+        ws = _wgrad_group_workspace(device, last.queue, need)
         plan.hold(arr, ws)
-        replaced[r[-1]] = (lib.combat_conv_wgrad_group, (arr, len(r), ws.data_ptr(), ws.numel()), "+".join(plan.calls[c][2] for c in r))
-        dropped.update(r[:-1])
-        for c in r[:-1]:
-            args_of[c] = None
-    assert not (dropped & set(plan.marks)), "an all-reduce mark on a weight-gradient call"
-    new_index, calls = {}, []
-    last_of = {c: r[-1] for r in runs for c in r}
-    for ci, call in enumerate(plan.calls):
-        if ci in dropped:
-            continue
-        new_index[ci] = len(calls)
-        calls.append(replaced.get(ci, call))
-    at = lambda ci: new_index[last_of.get(ci, ci)]
-    plan.calls = calls
-    plan.marks = {at(ci): off for ci, off in plan.marks.items()}
-    plan.aux = {at(ci): q for ci, q in plan.aux.items() if ci not in dropped}
-    plan.after = {at(ci): at(dep) for ci, dep in plan.after.items()}
-    plan.wgrads = [(at(ci), a) for ci, a in plan.wgrads]
-    plan.pending_reduces = [(w, a, at(ci)) for w, a, ci in plan.pending_reduces]
-    plan._prog = None
+        last.func, last.args = lib.combat_conv_wgrad_group, (arr, len(r), ws.data_ptr(), ws.numel())
+        last.what, last.wgrad = "+".join(c.what for c in r), [c.wgrad for c in r]
+        dropped.update((c, last) for c in r[:-1])
+    assert all(c.mark is None for c in dropped), "an all-reduce mark on a weight-gradient call"
+    plan.calls = [c for c in plan.calls if c not in dropped]
+    plan.pending_reduces = [(w, a, dropped.get(c, c)) for w, a, c in plan.pending_reduces]
+    plan._changed()
 
 
 _WGRAD_WS: Dict = {}
@@ -1968,7 +1962,7 @@ class CUnetEngine(UnetEngine):
         P.hold(taps, y, dw, d)
         # auxiliary like the bias column sums: consumed by the optimiser only
         P.add("cond.wgrad", lib.combat_cond_wgrad, d.data_ptr(), y.data_ptr(), slot.N, d.shape[1], nf, self.num_classes,
-              self.dwf01.data_ptr(), dw.data_ptr(), taps.data_ptr(), aux=True, after=len(P.calls) - 1)
+              self.dwf01.data_ptr(), dw.data_ptr(), taps.data_ptr(), aux=True, after=P.calls[-1])
 
 
 # --------------------------------------------------------------------------------------------

@@ -153,7 +153,7 @@ def backward_allreduce(plan, eng, pg, world: int, reducers: dict, prof=None) -> 
         return
     red = reducers.get(id(plan))
     if red is None:
-        ranges = bucket_ranges(eng.fp.total, plan.marks.values())
+        ranges = bucket_ranges(eng.fp.total, plan.mark_offsets)
         red = (GradReducer(eng.fp.grad, ranges, pg), ranges)
         reducers[id(plan)] = red
     reducer, ranges = red

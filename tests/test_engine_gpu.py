@@ -540,7 +540,7 @@ def test_backward_plans_do_not_share_weight_gradient_scratch(mods):
         eg.forward_plan(sg2).run()
         sg2.buf("g.z", (128, 32, 32, 8)).copy_(z)
         gb2 = eg.backward_plan(sg2)
-        assert gb2.aux_queues == 2 and set(gb2.aux.values()) == {0, 1}
+        assert gb2.aux_queues == 2 and {c.queue for c in gb2.calls if c.queue is not None} == {0, 1}
         for rep in range(3):
             got = grads(eg.fp, gnames, gb2.run)
             for k in gnames:
@@ -586,13 +586,14 @@ def test_deferred_weight_gradient_reductions(mods):
         behind = build("defer.behind", False)
     finally:
         engine.REDUCE_BEHIND = False
-    n_red = sum(1 for f, _, _ in plan.calls if f is lib.combat_conv_wgrad_reduce)
-    assert n_red >= 12 and len(plan.after) == n_red and not any(f is lib.combat_conv_wgrad_reduce for f, _, _ in ref_plan.calls)
+    n_red = sum(1 for c in plan.calls if c.func is lib.combat_conv_wgrad_reduce)
+    assert n_red >= 12 and sum(1 for c in plan.calls if c.after is not None) == n_red
+    assert not any(c.func is lib.combat_conv_wgrad_reduce for c in ref_plan.calls)
     # reduce-behind (round 4, opt-in): the slab-leaving launches form ONE chain per plan -- each carries its
     # predecessor (reduce_first), only the last one gets a reduction call
-    chained = [a for _, a in behind.wgrads if a.defer_reduce]
+    chained = [a for a in behind.wgrads if a.defer_reduce]
     assert len(chained) == n_red and sum(1 for a in chained if a.reduce_first) == n_red - 1
-    assert sum(1 for f, _, _ in behind.calls if f is lib.combat_conv_wgrad_reduce) == 1
+    assert sum(1 for c in behind.calls if c.func is lib.combat_conv_wgrad_reduce) == 1
     ref = grads(ref_plan.run)
     first = grads(behind.run)
     for k in names:
@@ -930,7 +931,7 @@ def test_preact_train_forward_with_lds_prologue_equals_the_chain(mods):
             eng.head_bufs(slot)["targets"].copy_(t)
             with engine.short_workgroups():       # (ring tiles in both modes: the persistent kernel groups its statistics rows differently)
                 fwd, bwd = eng.forward_plan(slot, True), eng.backward_train_plan(slot)
-            names = [w for _, _, w in fwd.calls]
+            names = [c.what for c in fwd.calls]
             assert any(w.endswith(".finalize") for w in names) == fused
             assert sum(w.endswith(".finact") for w in names) == (3 if fused else 16)      # the stride-2 blocks' inputs stay materialised
             fwd.run()
@@ -968,7 +969,7 @@ def test_fused_head_plans_equal_the_two_launch_plans(mods):
         eng.head_bufs(slot)["targets"].copy_(t)
         kw_f, kw_b = (dict(head_bwd=True), dict(head_done=True)) if fused else ({}, {})
         fwd, bwd = eng.forward_plan(slot, True, **kw_f), eng.backward_train_plan(slot, **kw_b)
-        assert sum("head" in w for _, _, w in fwd.calls) == 1 and any(w == "head_bwd.w" for _, _, w in bwd.calls) == fused
+        assert sum("head" in c.what for c in fwd.calls) == 1 and any(c.what == "head_bwd.w" for c in bwd.calls) == fused
         fwd.run()
         bwd.run()
         torch.cuda.synchronize()

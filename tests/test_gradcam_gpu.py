@@ -246,7 +246,7 @@ FWD_NAMES = ["stem"] + [name for b in range(8) for name in
 
 
 def names(plan):
-    return [call[2] for call in plan.calls]
+    return [call.what for call in plan.calls]
 
 
 def test_default_plans_are_built_as_before(m, net):

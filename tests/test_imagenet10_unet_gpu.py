@@ -43,7 +43,7 @@ def test_unet_plan_names_unchanged_at_hw32():
     from combat_amd import nets
     eng = seeded(lambda: nets.UnetGenerator(None), 3).cuda()._net_engine()
     slot = eng.slot("names", 2, 32)
-    got = tuple(" ".join(what for _, _, what in p.calls) for p in (eng.forward_plan(slot), eng.backward_plan(slot)))
+    got = tuple(" ".join(c.what for c in p.calls) for p in (eng.forward_plan(slot), eng.backward_plan(slot)))
     assert got == PLAN_NAMES_HW32
 
 

@@ -56,7 +56,7 @@ def flat_grad(eng, plan, **kw):
 
 
 def groups_of(lib, plan):
-    return [(i, what.split("+")) for i, (f, _, what) in enumerate(plan.calls) if f is lib.combat_conv_wgrad_group]
+    return [(i, c.what.split("+")) for i, c in enumerate(plan.calls) if c.func is lib.combat_conv_wgrad_group]
 
 
 @pytest.mark.parametrize("mode", ["tail", "pairs", "stages"])
@@ -78,7 +78,7 @@ def test_grouped_backward_equals_ungrouped_bitwise(net, mode):
     for rep in range(2):
         assert torch.equal(flat_grad(eng, on), ref), (mode, rep)
     # the plan still lists every weight gradient, in the order it was recorded, with the gradient it writes
-    assert [a.dw for _, a in on.wgrads] == [a.dw for _, a in off.wgrads]
+    assert [a.dw for a in on.wgrads] == [a.dw for a in off.wgrads]
 
 
 def test_grouped_backward_python_and_inline_replay(net):
@@ -118,9 +118,9 @@ def test_no_group_spans_an_all_reduce_mark(net):
     lib, eng = net["lib"], net["eng"]
     _, off = net["build"]("off", True)
     _, on = net["build"]("stages", True)
-    assert on.flush_at_marks and len(on.marks) == len(off.marks) == len(MARK_BLOCKS) + 1
-    where = {what: i for i, (_, _, what) in enumerate(off.calls)}
-    stage = lambda plan, i: sum(1 for m in plan.marks if m < i)
+    assert on.flush_at_marks and len(on.mark_offsets) == len(off.mark_offsets) == len(MARK_BLOCKS) + 1
+    where = {c.what: i for i, c in enumerate(off.calls)}
+    stage = lambda plan, i: sum(1 for c in plan.calls[:i] if c.mark is not None)
     groups = groups_of(lib, on)
     assert len(groups) == 4
     for i, members in groups:
@@ -128,8 +128,8 @@ def test_no_group_spans_an_all_reduce_mark(net):
         assert stage(on, i) == stage(off, where[members[0]]), members
         assert where[members[-1]] == max(where[w] for w in members)
     # the marks keep their gradient offsets and their order
-    assert [on.marks[i] for i in sorted(on.marks)] == [off.marks[i] for i in sorted(off.marks)]
+    assert on.mark_offsets == off.mark_offsets
     seen = []
     ref = flat_grad(eng, off)
     got = flat_grad(eng, on, on_mark=seen.append)
-    assert torch.equal(got, ref) and seen == [on.marks[i] for i in sorted(on.marks)]
+    assert torch.equal(got, ref) and seen == on.mark_offsets

@@ -18,11 +18,11 @@ for k in dir(lib):
 rec = []
 def run(self, prof=None, on_mark=None):
     s = torch.cuda.current_stream(); stp = s.cuda_stream
-    for ci, (cfunc, args, what) in enumerate(self.calls):
+    for c in self.calls:
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-        e0.record(s); rc = cfunc(*args, stp); e1.record(s)
+        e0.record(s); rc = c.func(*c.args, stp); e1.record(s)
         assert rc == 0
-        rec.append((self.name, what, getattr(cfunc, "__name__", None) or names.get(id(cfunc), "?"), e0, e1))
+        rec.append((self.name, c.what, getattr(c.func, "__name__", None) or names.get(id(c.func), "?"), e0, e1))
 Plan.run = run
 st.serial = Plan.serial = True
 for i in range(3): st.run(*batches[i])

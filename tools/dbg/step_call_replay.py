@@ -24,7 +24,8 @@ torch.cuda.synchronize()
 P = st.pl["C_train_f"]
 s0 = torch.cuda.current_stream().cuda_stream
 bufs = st.sC_train.bufs
-for i, (cfunc, args, what) in enumerate(P.calls[:12]):
+for i, c in enumerate(P.calls[:12]):
+    cfunc, args, what = c.func, c.args, c.what
     if cfunc is lib.combat_conv_gemm:
         a = args[0]._obj
         print(i, what, "tile", lib.combat_conv_pick_tile(ctypes.byref(a)), "pro", bool(a.pro_scale), "side", bool(a.pro_act_dst), "stats_kind", a.stats_kind,
@@ -49,15 +50,14 @@ for i, (cfunc, args, what) in enumerate(P.calls[:12]):
 for k in (3, 4, 5):
     res = []
     for r in range(6):
-        for (cfunc, args, what) in P.calls[:k]:
-            cfunc(*args, s0)
+        for c in P.calls[:k]:
+            c.func(*c.args, s0)
         torch.cuda.synchronize()
         res.append(bufs["b0.y1"].clone())
-    print("prefix", k, [w for _, _, w in P.calls[:k]][-1], "b0.y1 deterministic:", all(torch.equal(res[0], r_) for r_ in res))
+    print("prefix", k, P.calls[k - 1].what, "b0.y1 deterministic:", all(torch.equal(res[0], r_) for r_ in res))
 # ---- bisect call 2: change one field at a time
 import copy
-cfunc, args, what = P.calls[2]
-a0_ = args[0]._obj
+a0_ = P.calls[2].args[0]._obj
 def variant(name, **kw):
     a = ConvArgs()
     ctypes.memmove(ctypes.byref(a), ctypes.byref(a0_), ctypes.sizeof(ConvArgs))

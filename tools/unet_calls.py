@@ -14,16 +14,16 @@ torch.cuda.synchronize()
 plan = st.pl[sys.argv[1] if len(sys.argv) > 1 else "G_f"]
 s = torch.cuda.current_stream(); stp = s.cuda_stream
 seq = []
-for cfunc, args, what in plan.calls:
+for c in plan.calls:
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(s); cfunc(*args, stp); e1.record(s)
-    seq.append((what, e0, e1))
+    e0.record(s); c.func(*c.args, stp); e1.record(s)
+    seq.append((c.what, e0, e1))
 torch.cuda.synchronize()
-for (cfunc, args, what), (_, e0, e1) in zip(plan.calls, seq):
+for c, (what, e0, e1) in zip(plan.calls, seq):
     t_seq = e0.elapsed_time(e1) * 1e3
     torch.cuda.synchronize()
     a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a0.record(s)
-    for _ in range(20): cfunc(*args, stp)
+    for _ in range(20): c.func(*c.args, stp)
     a1.record(s); torch.cuda.synchronize()
     print("%-28s in sequence %6.1f us   alone, back to back %6.1f us" % (what, t_seq, a0.elapsed_time(a1) * 1e3 / 20))
