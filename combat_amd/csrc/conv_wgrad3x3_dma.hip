@@ -673,8 +673,7 @@ int pick_split(const combat_wgrad_args *a, const W3dParams &p, bool with_ws) {
     const int base = p.tiles_k * p.tiles_c;
     int split = a->split;
     if (split <= 0) {
-        static const int ws_wgs = getenv("COMBAT_WGRAD_WGS") ? atoi(getenv("COMBAT_WGRAD_WGS")) : 128;   // (experiments)
-        const int by_cus = ((with_ws ? ws_wgs : 256) + base - 1) / base;
+        const int by_cus = ((with_ws ? 128 : 256) + base - 1) / base;
         const int by_atomics = 164 / base > 0 ? 164 / base : 1;
         split = with_ws || by_cus < by_atomics ? by_cus : by_atomics;
         const int by_work = (p.ntiles + 3) / 4;

@@ -19,15 +19,15 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import ops
-from ._lib import STATS_PER_WORKGROUP, TILE_D128x32, TILE_D128x64, TILE_S128x64, CombatHipError, ConvArgs, lib
+from ._lib import STATS_PER_WORKGROUP, TILE_D128x64, TILE_S128x64, CombatHipError, ConvArgs, lib  # noqa: F401  (ConvArgs: re-exported)
 from .nets import UNET_LAYERS
 from .ops import Affine, PackedConv, bf16
 
 # Statistics over the whole batch (BatchNorm) ask the convolution for one partial row per workgroup instead of one per
 # wave: 256 rows instead of 1024-4096 on the 32 x 32 and 16 x 16 layers, so the fused normalisation launches reduce them
 # themselves and no norm_stage1 launch stands between a convolution and its normalisation (18 launches per alternated
-# step).  COMBAT_STATS_PER_WAVE=1 restores the per-wave rows (A/B measurements).
-BATCH_STATS_ROWS = 0 if os.environ.get("COMBAT_STATS_PER_WAVE") == "1" else STATS_PER_WORKGROUP
+# step).
+BATCH_STATS_ROWS = STATS_PER_WORKGROUP
 
 f32 = torch.float32
 
@@ -55,16 +55,6 @@ class Plan:
     serial = False   # True: auxiliary-stream calls run in line (kernel-level measurements: one kernel at a time)
     serial_shortcuts = False   # True: shortcut input gradients as launches of their own (per-launch profiling, A/B)
     default_aux_queues = 1   # auxiliary queues a new plan deals its aux calls to (see aux_queues below)
-    flush_at_marks = False   # data parallel: deferred weight-gradient reductions are issued at every all-reduce mark
-    #                          (the gradients above a mark must be final there); otherwise all of them at the end of
-    #                          the plan, on its own stream, each behind its weight gradient only
-    # Deferred weight-gradient reductions (combat_wgrad_args.defer_reduce + Plan.flush_reduces) are OFF by default:
-    # measured on the alternated step (tools/quick_step.py, same box, same process order) 4.31 ms/step with every
-    # reduction right behind its kernel on the auxiliary queue, 4.45-4.51 with the reductions on the plan's own stream
-    # behind per-call events (private 19-MB slab regions or a ring of two: no difference; private regions WITHOUT
-    # deferral: 4.32, so it is not the slabs leaving the Infinity Cache) -- twenty event records between the auxiliary
-    # queue's kernels and twenty cross-queue waits cost more than the 8-us reductions they take off that queue.
-    defer_reduces = os.environ.get("COMBAT_DEFER_REDUCE", "0") == "1"
     # Same-geometry weight gradients that follow each other on an auxiliary queue as ONE combat_conv_wgrad_group call
     # (group_wgrads below).  COMBAT_WGRAD_GROUP = off | tail (only the plan's last run of layers: PreActResNet18's four
     # layer1 convolutions) | pairs (two members at most, last stage only) | stages (every run inside a stage).  The
@@ -81,9 +71,6 @@ class Plan:
         self._ws = None
         self._cplan = None                # combat_plan* of the compiled form (built on first run)
         self._prog = None
-        self.pending_reduces: List[Tuple] = []   # (what, WgradArgs, its weight-gradient Call)
-        self.chain: Dict[int, Tuple] = {}        # auxiliary queue -> (what, WgradArgs) of the launch whose slabs await the next one
-        self.chain_count: Dict[int, int] = {}    # auxiliary queue -> slab-leaving launches so far (alternates the two regions)
 
     def add(self, what: str, cfunc, *args, aux: bool = False, after: Optional[Call] = None) -> Call:
         """aux: the call's result is only consumed after the plan (weight gradients: by the optimiser /
@@ -106,16 +93,6 @@ class Plan:
     def wgrads(self) -> List:
         """Every WgradArgs of the plan in recorded order (the members of a grouped call one by one)."""
         return [a for c in self.calls if c.wgrad is not None for a in (c.wgrad if isinstance(c.wgrad, list) else [c.wgrad])]
-
-    def flush_reduces(self) -> None:
-        """Issue the reductions of the weight gradients recorded with defer_reduce so far: on the plan's own stream,
-        each waiting for its weight-gradient launch only.  The auxiliary queue then holds a chain of weight-gradient
-        kernels instead of (kernel, reduction) pairs -- the reductions were 10 of every 40 us of what is the critical
-        path of both training backward passes -- and the reductions run while it works on the next layers."""
-        for what, a, call in self.pending_reduces:
-            self.add(what, lib.combat_conv_wgrad_reduce, ctypes.byref(a), after=call)
-        self.pending_reduces = []
-        self.chain = {}      # (reduce-behind: the chains' last launches were in the list above; the next launch starts a new chain)
 
     def next_aux_queue(self) -> int:
         """Queue the next aux call will be given (round-robin over `aux_queues`)."""
@@ -143,8 +120,6 @@ class Plan:
 
     def mark(self, grad_offset: int) -> None:
         """Every gradient at flat offset >= grad_offset is final once the calls recorded so far ran."""
-        if self.flush_at_marks or grad_offset == 0:
-            self.flush_reduces()
         self.calls[-1].mark = grad_offset
         self._changed()
 
@@ -339,23 +314,6 @@ def _aux_pointers(parent: torch.cuda.Stream, n: int):
     return arr
 
 
-_HIP = None
-
-
-def low_priority_stream(dev) -> torch.cuda.Stream:
-    """A stream of the LOWEST priority the device offers (torch only exposes normal / high)."""
-    global _HIP
-    if _HIP is None:
-        _HIP = ctypes.CDLL("libamdhip64.so")
-    least, greatest = ctypes.c_int(), ctypes.c_int()
-    assert _HIP.hipDeviceGetStreamPriorityRange(ctypes.byref(least), ctypes.byref(greatest)) == 0
-    h = ctypes.c_void_p()
-    with torch.cuda.device(dev):
-        assert _HIP.hipStreamCreateWithPriority(ctypes.byref(h), 1, least.value) == 0      # 1 = hipStreamNonBlocking
-    print("low-priority stream: range least %d greatest %d" % (least.value, greatest.value), flush=True)
-    return torch.cuda.ExternalStream(h.value, device=dev)
-
-
 def _aux_stream(parent: torch.cuda.Stream, k: int = 0) -> torch.cuda.Stream:
     """The auxiliary stream of the stream a plan runs on, for calls marked aux (weight gradients beside
     the input-gradient chain).  Per parent stream: two chains that run concurrently must not order each
@@ -365,10 +323,7 @@ def _aux_stream(parent: torch.cuda.Stream, k: int = 0) -> torch.cuda.Stream:
     key = (parent.device, parent.cuda_stream, k)
     s = _AUX_STREAMS.get(key)
     if s is None:
-        if os.environ.get("COMBAT_LOW_PRIO_SIDE", "0") == "1":
-            s = low_priority_stream(parent.device)
-        else:
-            s = torch.cuda.Stream(device=parent.device)
+        s = torch.cuda.Stream(device=parent.device)
         _AUX_STREAMS[key] = s
     return s
 
@@ -533,22 +488,6 @@ def _tile_preference(a) -> None:
 
 
 FUSE_SHORTCUT = os.environ.get("COMBAT_NO_FUSED_SHORTCUT", "0") != "1"
-# COMBAT_REDUCE_BEHIND=1: a weight gradient's slab reduction rides in the NEXT weight-gradient launch of its queue
-# (rec_wgrad, combat_wgrad_args.reduce_first): 23 of the 24 reduction launches of a step disappear and the 3x3 weight
-# gradients become bit-reproducible (fixed summation order, no atomics).  OFF by default: measured 3.84 against 3.74
-# ms/step -- the 128 workgroups of a weight gradient fold 147 KB of slabs each at a CU's ~30 GB/s before their first
-# patch (+8 us per launch, +18 on the 512-channel layers), the round-3 reduction launch spreads the same bytes over the
-# whole chip in 4-8 us (tools/wgrad_chain_bench.py).
-REDUCE_BEHIND = os.environ.get("COMBAT_REDUCE_BEHIND", "0") == "1"
-# COMBAT_FUSED_PROLOGUE=1: train-mode BatchNorm + ReLU applied by the CONSUMING convolution in LDS
-# (PreActEngine._forward_train_body, conv3x3_dma_pro_kernel) instead of one combat_norm_act_fused launch per BatchNorm.
-# OFF by default: built, bit-identical (tests/test_kernels_gpu.py::test_conv_lds_prologue_equals_norm_act_then_conv) and
-# measured SLOWER -- 3.885 against 3.757 ms/step on one box (profiles/r04_a_*): every channel tile of the consumer
-# repeats the transform (16x on a 512-channel layer with 32-channel tiles), the patch of a 4 x 4 map is three times
-# its pixels, and the 64-channel layers lose the weight-stationary kernel; tools/pro_bench.py has the per-shape table
-# (back to back: +3.8 us on 64 -> 64 @ 32 x 32, +9 on 256 -> 256 @ 8 x 8, +17 on 512 -> 512 @ 4 x 4, against
-# 4-7 us for the stand-alone activation pass).  DESIGN.md section 5, round 4.
-FUSED_PROLOGUE = os.environ.get("COMBAT_FUSED_PROLOGUE", "0") == "1"
 
 
 def fuse_shortcut(dy, dx, pc: PackedConv, dy_sc, pc_sc: PackedConv):
@@ -584,34 +523,8 @@ def rec_wgrad(plan: Plan, what: str, src, dy, pc: PackedConv, dw, pro: Optional[
     queue = plan.next_aux_queue() if aux else -1
     ws = _wgrad_workspace(src.device, queue)
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    need = int(lib.combat_conv_wgrad_workspace_bytes(ctypes.byref(a)))
-    prev = plan.chain.get(queue) if aux else None
-    if aux and REDUCE_BEHIND and not Plan.defer_reduces and need > 0:      # (need > 0: the DMA-staged 3x3 kernel, several pixel ranges)
-        # Reduce-behind (round 4): a launch that leaves partial-sum slabs does not reduce them; the NEXT weight gradient
-        # of this queue folds them into this launch's dw before it starts on its own patches
-        # (combat_wgrad_args.reduce_first), and only the last one of a chain gets a reduction launch (Plan.flush_reduces).
-        # Slabs live in one of two private regions per queue, used alternately: the reader of region k % 2 (launch
-        # k + 1) has completed before launch k + 2 writes it.
-        if prev is not None:
-            a.reduce_first = ctypes.addressof(prev[1])
-            plan.pending_reduces = [q for q in plan.pending_reduces if q[1] is not prev[1]]
-            plan.hold(prev[1])
-            plan.chain.pop(queue)
-        k = plan.chain_count.get(queue, 0)
-        plan.chain_count[queue] = k + 1
-        ws = _wgrad_slab_region(src.device, queue, k % 2, need)
-        a.workspace, a.workspace_bytes, a.defer_reduce = ws.data_ptr(), ws.numel(), 1
-        plan.chain[queue] = (what, a)
-    elif aux and need > 0 and Plan.defer_reduces:
-        # a launch that leaves partial-sum slabs: its reduction is deferred (Plan.flush_reduces), so the slabs need a
-        # region of their own until then -- HBM is 288 GB, a backward plan's ~20 regions of 19 MB are not
-        ws = torch.empty(need, dtype=torch.uint8, device=src.device)
-        a.workspace, a.workspace_bytes, a.defer_reduce = ws.data_ptr(), need, 1
     plan.hold(a, src, dy, dw, pro, ws)
-    call = plan.add(what, lib.combat_conv_wgrad, ctypes.byref(a), aux=aux)
-    call.wgrad = a
-    if a.defer_reduce:
-        plan.pending_reduces.append((what + ".reduce", a, call))
+    plan.add(what, lib.combat_conv_wgrad, ctypes.byref(a), aux=aux).wgrad = a
 
 
 def set_deterministic(on: bool) -> None:
@@ -626,39 +539,6 @@ def set_deterministic(on: bool) -> None:
 def deterministic() -> bool:
     return bool(lib.combat_get_deterministic())
 
-
-_WGRAD_SLABS: Dict = {}
-
-
-def _wgrad_slab_region(device, queue: int, which: int, need: int) -> torch.Tensor:
-    """One of the two slab regions of a queue's reduce-behind chain (rec_wgrad)."""
-    key = (device, int(queue), int(which))
-    t = _WGRAD_SLABS.get(key)
-    if t is None or t.numel() < need:
-        t = torch.empty(max(need, 24 << 20), dtype=torch.uint8, device=device)
-        _WGRAD_SLABS[key] = t
-    return t
-
-
-def balance_wgrads(plan: Plan, device) -> None:
-    """Weight gradients run on the auxiliary stream beside the input-gradient chain -- but they are the longer of
-    the two chains (20 launches of ~40 us against ~480 us of input gradients + norm backward in PreActResNet18's
-    backward), so the plan ended with the main stream idle behind ~400 us of queued weight gradients.  The LAST
-    `tail` weight gradients of the plan (the early layers) are therefore issued on the plan's own stream: at the
-    end of the plan both queues run weight gradients side by side (each is sized for half the chip)."""
-    tail = int(os.environ.get("COMBAT_WGRAD_MAIN_TAIL", WGRAD_MAIN_TAIL))
-    if tail <= 0 or Plan.serial:
-        return
-    aux_calls = [c for c in plan.calls if c.func is lib.combat_conv_wgrad and c.queue is not None]
-    ws = _wgrad_workspace(device, -1)
-    for c in aux_calls[-tail:]:
-        c.queue = None
-        c.wgrad.workspace, c.wgrad.workspace_bytes = ws.data_ptr(), ws.numel()
-        plan.hold(ws)
-    plan._changed()
-
-
-WGRAD_MAIN_TAIL = 0
 
 _WGRAD_GROUP_WS: Dict = {}
 
@@ -715,7 +595,7 @@ def group_wgrads(plan: Plan, device) -> None:
         runs = runs[-1:]
     elif mode == "pairs":
         runs = [r for r in runs if stage[r[0]] == stage[runs[-1][0]]]
-    dropped = {}          # member that leaves the list -> the call of its group
+    dropped = set()       # members that leave the list
     for r in runs:
         arr, need = query(r)
         last = r[-1]      # becomes the group call: its place, queue and mark stay
@@ -723,10 +603,9 @@ def group_wgrads(plan: Plan, device) -> None:
         plan.hold(arr, ws)
         last.func, last.args = lib.combat_conv_wgrad_group, (arr, len(r), ws.data_ptr(), ws.numel())
         last.what, last.wgrad = "+".join(c.what for c in r), [c.wgrad for c in r]
-        dropped.update((c, last) for c in r[:-1])
+        dropped.update(r[:-1])
     assert all(c.mark is None for c in dropped), "an all-reduce mark on a weight-gradient call"
     plan.calls = [c for c in plan.calls if c not in dropped]
-    plan.pending_reduces = [(w, a, dropped.get(c, c)) for w, a, c in plan.pending_reduces]
     plan._changed()
 
 
@@ -768,24 +647,6 @@ def _pow2_part(pq: int, cap: int = 32) -> int:
 
 class NetEngine:
     """Shared machinery: parameters, packed operands, scratch, slots."""
-
-    _flush_at_marks = False
-
-    @property
-    def flush_at_marks(self) -> bool:
-        """Set by a data-parallel step (see Plan.flush_at_marks).  Backward plans copy it when they are built and are
-        cached per slot, and an engine is shared by every step object of its module: changing the value drops the
-        cached backward plans, so that a plan built for a single-rank step is never replayed under all-reduce marks."""
-        return self._flush_at_marks
-
-    @flush_at_marks.setter
-    def flush_at_marks(self, value: bool) -> None:
-        value = bool(value)
-        if value != self._flush_at_marks:
-            for slot in getattr(self, "slots", {}).values():
-                for k in [k for k in slot.plans if k.startswith("bwd")]:
-                    del slot.plans[k]
-        self._flush_at_marks = value
 
     def __init__(self, module: torch.nn.Module):
         self.module = module
@@ -909,26 +770,6 @@ class NetEngine:
                  1e-5, _p(gamma), _p(beta), st.mean.data_ptr(), st.rstd.data_ptr(), st.scale.data_ptr(),
                  st.shift.data_ptr(), _p(rm), _p(rv), 0.1, _p(nbt), scr.data_ptr(), scr.numel() * 4)
         return st
-
-    def _lds_prologue_ok(self, src, pc: PackedConv) -> bool:
-        """Would a forward 3x3 convolution of `src` through `pc` with a per-channel BatchNorm + ReLU prologue and the
-        activated side output take the DMA-staged kernel that applies the prologue in LDS (combat_conv_args.pro_act_dst)?"""
-        if not FUSED_PROLOGUE or pc.R != 3 or pc.stride != 1:
-            return False
-        n, h, w, _ = src.shape
-        probe = getattr(self, "_pro_probe", None)
-        if probe is None:
-            t = torch.zeros(512, dtype=f32, device=self.device)
-            probe = self._pro_probe = Affine(t, t, 0, True, 0.0)
-        a = ConvArgs()
-        a.N, a.H, a.W, a.C = src.shape
-        a.P, a.Q, a.K = h, w, pc.Kc
-        a.R = a.S = 3
-        a.stride, a.pad, a.mode = 1, pc.pad, 0
-        a.src, a.dst, a.pro_act_dst = src.data_ptr(), src.data_ptr(), src.data_ptr()
-        a.wpack, a.kpad, a.rows_pad = pc.wf.data_ptr(), pc.kpad_f, pc.rows_f
-        a.pro_scale, a.pro_shift, a.pro_act = probe.scale.data_ptr(), probe.shift.data_ptr(), 1
-        return lib.combat_conv_pick_tile(ctypes.byref(a)) in (TILE_D128x64, TILE_D128x32)
 
     def _norm_act(self, plan: Plan, st: NormState, act_dst, slope: float):
         """The deferred finalize of `st` + its activation tensor, one launch."""
@@ -1086,8 +927,9 @@ class PreActEngine(NetEngine):
         """split_head (eval only): the batch is two independent halves [metric-only images ; images whose
         loss is differentiated]; the head runs once per half with separate loss / counter cells
         (first half -> correct[0] of slot 'loss0/correct0' cells, second half -> the usual ones).
-        head_bwd: the head launch also produces dlogits and the gradient w.r.t. the feature map ('g.feat':
-        combat_head_fwd_bwd), for a pass whose backward plan (built with head_done=True) follows at once.
+        head_bwd (eval only): the head launch also produces dlogits and the gradient w.r.t. the feature map ('g.feat':
+        combat_head_fwd_bwd), for a pass whose backward plan (backward_eval_plan(head_done=True)) follows at once; a
+        train-mode pass has no such backward and raises ValueError.
         two_loss (eval only): the batch is two halves whose losses are BOTH differentiated (the input-aware step's
         [aug(bd) ; aug(bd2)], labels targets[:n] / targets[n:]): first half -> the usual cells, second half ->
         'loss1' / 'correct1'; the matching backward is backward_eval_plan(half_weights=...).  Each half runs as the
@@ -1096,6 +938,8 @@ class PreActEngine(NetEngine):
         parameters and rounds differently.
         keep_raw_blocks (eval only, PreActEngine only): blocks whose raw output 'b%d.out' is written although no identity
         shortcut reads it (Grad-CAM taps it, combat_amd/defenses.py::GradCam); everything else is computed as without."""
+        if train and head_bwd:
+            raise ValueError("head_bwd: only an eval pass has a backward plan that starts behind the head (backward_eval_plan(head_done=True))")
         keep_raw_blocks = tuple(sorted(set(int(b) for b in keep_raw_blocks)))
         if keep_raw_blocks:
             if type(self) is not PreActEngine or train or two_loss:
@@ -1164,25 +1008,15 @@ class PreActEngine(NetEngine):
 
     def _forward_train_body(self, P: Plan, slot: Slot, x):
         """Train mode: BatchNorm uses batch statistics, produced by the epilogue of the convolution that
-        writes the normalised tensor.  relu(bn(.)) is then materialised once per BatchNorm ('b%d.a0' =
-        block input through bn1, 'b%d.a1t' = conv1 output through bn2): the forward convolutions and
-        the weight-gradient passes that read it need no prologue and take their operands by LDS-DMA.
-
-        Round 4 (FUSED_PROLOGUE): where the consumer is a 3x3 / stride-1 convolution, relu(bn(.)) is not a launch of
-        its own any more: the producer's statistics are finalised (per-channel scale / shift) and the CONSUMING
-        convolution applies them in LDS after its DMA'd patch has landed (combat_conv_args.pro_* on the DMA-staged
-        kernel), writing the activated tensor out on the side for its weight gradient (pro_act_dst).  The blocks with
-        a stride-2 first convolution + 1x1 shortcut still get their input materialised by combat_norm_act_fused."""
+        writes the normalised tensor.  relu(bn(.)) is then materialised once per BatchNorm by its
+        combat_norm_act_fused launch ('b%d.a0' = block input through bn1, 'b%d.a1t' = conv1 output through
+        bn2): the forward convolutions and the weight-gradient passes that read it need no prologue and take
+        their operands by LDS-DMA."""
         n, hw = slot.N, slot.hw
         cur = slot.buf("stem", (n, hw, hw, 64))
-
-        def fuse(blk, src):    # does blk.conv1 read its raw input `src` with the in-LDS prologue?
-            return blk.sc is None and blk.stride == 1 and self._lds_prologue_ok(src, blk.conv1)
-
-        first = self.blocks[0].bn1
+        bnk = lambda bn: dict(groups=1, gamma=bn.gamma, beta=bn.beta, running=(bn.rm, bn.rv, bn.nbt))
         a0 = slot.buf("b0.a0", cur.shape)
-        st = self._conv_norm(P, slot, first.prefix, x, cur, self.stem, groups=1, gamma=first.gamma, beta=first.beta,
-                             running=(first.rm, first.rv, first.nbt), act_dst=None if fuse(self.blocks[0], cur) else a0)
+        self._conv_norm(P, slot, self.blocks[0].bn1.prefix, x, cur, self.stem, act_dst=a0, **bnk(self.blocks[0].bn1))
         chw = hw
         for b, blk in enumerate(self.blocks):
             ohw = chw // blk.stride
@@ -1194,31 +1028,16 @@ class PreActEngine(NetEngine):
                 resid = cur
             y1 = slot.buf("b%d.y1" % b, (n, ohw, ohw, blk.planes))
             out = slot.buf("b%d.out" % b, (n, ohw, ohw, blk.planes))
-            nxt = self.blocks[b + 1].bn1 if b + 1 < len(self.blocks) else None
             a1 = slot.buf("b%d.a1t" % b, y1.shape)
-            fuse2 = self._lds_prologue_ok(y1, blk.conv2)
-            bn2 = dict(groups=1, gamma=blk.bn2.gamma, beta=blk.bn2.beta, running=(blk.bn2.rm, blk.bn2.rv, blk.bn2.nbt),
-                       act_dst=None if fuse2 else a1)
-            if fuse(blk, cur):     # conv1 normalises + activates its raw input in LDS and leaves a0 for its weight gradient
-                st2 = self._conv_norm(P, slot, blk.bn2.prefix, cur, y1, blk.conv1, **bn2,
-                                      pro=Affine(st.scale, st.shift, 0, True, 0.0), pro_act_dst=a0)
-            else:
-                st2 = self._conv_norm(P, slot, blk.bn2.prefix, a0, y1, blk.conv1, **bn2)
+            self._conv_norm(P, slot, blk.bn2.prefix, a0, y1, blk.conv1, act_dst=a1, **bnk(blk.bn2))
             if blk.sc is not None:      # shortcut + first convolution: one launch (both read a0)
                 P.merge_convs(i_sc)
-            # conv2 is 3x3 / stride 1 in every block: relu(bn2(y1)) in LDS, a1 on the side
-            c2 = dict(add_post=resid)
-            src2 = a1
-            if fuse2:
-                c2.update(pro=Affine(st2.scale, st2.shift, 0, True, 0.0), pro_act_dst=a1)
-                src2 = y1
-            if nxt is not None:
+            if b + 1 < len(self.blocks):
+                nxt = self.blocks[b + 1].bn1
                 a0 = slot.buf("b%d.a0" % (b + 1), out.shape)
-                st = self._conv_norm(P, slot, nxt.prefix, src2, out, blk.conv2, groups=1, gamma=nxt.gamma, beta=nxt.beta,
-                                     running=(nxt.rm, nxt.rv, nxt.nbt),
-                                     act_dst=None if fuse(self.blocks[b + 1], out) else a0, **c2)
+                self._conv_norm(P, slot, nxt.prefix, a1, out, blk.conv2, act_dst=a0, add_post=resid, **bnk(nxt))
             else:
-                rec_conv(P, "b%d.c2" % b, src2, out, blk.conv2, 0, **c2)
+                rec_conv(P, "b%d.c2" % b, a1, out, blk.conv2, 0, add_post=resid)
             cur, chw = out, ohw
         return cur, chw
 
@@ -1263,46 +1082,33 @@ class PreActEngine(NetEngine):
         xin = slot.bufs["stem"] if b == 0 else slot.bufs["b%d.out" % (b - 1)]
         return xin, slot.bufs["b%d.y1" % b], slot.bufs["b%d.out" % b]
 
-    def backward_train_plan(self, slot: Slot, loss_weight: float = 1.0, head_done: bool = False) -> Plan:
+    def backward_train_plan(self, slot: Slot, loss_weight: float = 1.0) -> Plan:
         """Backward of a train-mode forward: all parameter gradients (into fp.grad, which the plan
-        zeroes first); no input gradient (Phase C never needs it, train_generator.py:220).
-        head_done: the forward plan was built with head_bwd=True -- dlogits and 'g.feat' exist; the linear layer's
-        weight gradient is then an auxiliary-queue launch behind the first input-gradient launch."""
-        key = "bwd.train.%g%s" % (loss_weight, ".hd" if head_done else "")
+        zeroes first); no input gradient (Phase C never needs it, train_generator.py:220)."""
+        key = "bwd.train.%g" % loss_weight
         if key in slot.plans:
             return slot.plans[key]
         P = Plan("preact." + key)
-        P.flush_at_marks = self.flush_at_marks
         fp, n = self.fp, slot.N
         h = self.head_bufs(slot)
         P.add("zero_grad", _zero_grad_call, fp)
         feat = slot.bufs["b%d.out" % (len(self.blocks) - 1)]
         d_out = slot.buf("g.feat", feat.shape)
-        if not head_done:
-            P.add("head_bwd", lib.combat_head_bwd, h["pooled"].data_ptr(), n, slot.feat_hw, feat.shape[-1],
-                  self.lin_w.data_ptr(), self.classes, h["logits"].data_ptr(), h["targets"].data_ptr(), loss_weight,
-                  h["dlogits"].data_ptr(), d_out.data_ptr(), fp.grad_phys("linear.weight").data_ptr(),
-                  fp.grad_phys("linear.bias").data_ptr())
-        head_w_pending = head_done
+        P.add("head_bwd", lib.combat_head_bwd, h["pooled"].data_ptr(), n, slot.feat_hw, feat.shape[-1],
+              self.lin_w.data_ptr(), self.classes, h["logits"].data_ptr(), h["targets"].data_ptr(), loss_weight,
+              h["dlogits"].data_ptr(), d_out.data_ptr(), fp.grad_phys("linear.weight").data_ptr(),
+              fp.grad_phys("linear.bias").data_ptr())
         for b in reversed(range(len(self.blocks))):
             blk = self.blocks[b]
             xin, y1, _ = self._block_io(slot, b)
             st1, st2 = slot.norm[blk.bn1.prefix], slot.norm[blk.bn2.prefix]
             a0, a1 = slot.bufs["b%d.a0" % b], slot.bufs["b%d.a1t" % b]   # relu(bn1(xin)), relu(bn2(y1)) of the forward
             pre = blk.prefix
-            if not head_w_pending:
-                rec_wgrad(P, "b%d.c2.wgrad" % b, a1, d_out, blk.conv2, fp.grad_phys(pre + "conv2.weight"))
+            rec_wgrad(P, "b%d.c2.wgrad" % b, a1, d_out, blk.conv2, fp.grad_phys(pre + "conv2.weight"))
             dz2 = slot.buf("g.b%d.dz2" % b, y1.shape)
             self._dgrad_norm(P, slot, "g." + blk.bn2.prefix, d_out, dz2, blk.conv2, y1, st2, group_stride=0,
                              slope=0.0, gamma=blk.bn2.gamma, dgamma=fp.grad_phys(pre + "bn2.weight"),
                              dbeta=fp.grad_phys(pre + "bn2.bias"))
-            if head_w_pending:    # (auxiliary calls behind the plan's first kernel launch: it carries their hand-off event)
-                head_w_pending = False
-                P.hold(h)
-                P.add("head_bwd.w", lib.combat_head_bwd_weights, h["dlogits"].data_ptr(), h["pooled"].data_ptr(), n, slot.feat_hw,
-                      feat.shape[-1], self.classes, fp.grad_phys("linear.weight").data_ptr(), fp.grad_phys("linear.bias").data_ptr(),
-                      aux=True)
-                rec_wgrad(P, "b%d.c2.wgrad" % b, a1, d_out, blk.conv2, fp.grad_phys(pre + "conv2.weight"))
             dy1 = slot.buf("g.b%d.dy1" % b, y1.shape)
             self._bwd_apply(P, slot, "g." + blk.bn2.prefix, dz2, y1, dy1, st2)
             tsc, fused = None, None
@@ -1325,7 +1131,6 @@ class PreActEngine(NetEngine):
                 P.mark(fp.offsets[pre + "bn1.weight"][0])
         rec_wgrad(P, "stem.wgrad", self.input(slot), d_out, self.stem, fp.grad_phys("conv1.weight"), aux=False)
         P.mark(0)
-        balance_wgrads(P, self.device)
         group_wgrads(P, self.device)
         slot.plans[key] = P
         return P
@@ -1364,7 +1169,8 @@ class PreActEngine(NetEngine):
                            stop_before: Optional[int] = None) -> Plan:
         """Backward of an eval-mode forward w.r.t. the input image only (Phase G: the classifier
         and clean-model weight gradients are never consumed, train_generator.py:179,254).
-        Result: slot buffer 'g.img' (bf16 NHWC c8, channels 0..2).  head_done: as backward_train_plan.
+        Result: slot buffer 'g.img' (bf16 NHWC c8, channels 0..2).  head_done: the forward plan was built with
+        head_bwd=True -- dlogits and 'g.feat' exist, and the plan records no head launch.
         half_weights (w0, w1): the backward of a two_loss forward -- each half's mean loss with its weight (loss_weight
         is then unused), each half through its n-image plan.
         stop_before b: the plan ends after block b's input-gradient launch and runs no stem dgrad.  Result: 'g.b%d.dx' % b,
@@ -1554,7 +1360,6 @@ class ResNetEngine(PreActEngine):
         if key in slot.plans:
             return slot.plans[key]
         P = Plan("resnet." + key)
-        P.flush_at_marks = self.flush_at_marks
         fp = self.fp
         G = lambda name, like: slot.buf("g." + name, like.shape)
         P.add("zero_grad", _zero_grad_call, fp)
@@ -1812,7 +1617,6 @@ class UnetEngine(NetEngine):
         if "bwd" in slot.plans:
             return slot.plans["bwd"]
         P = Plan("unet.bwd")
-        P.flush_at_marks = self.flush_at_marks
         fp, n, hw, nf = self.fp, slot.N, slot.hw, self.nf
         pc = self.pc
         t = lambda name: slot.bufs["t." + name]
@@ -1896,7 +1700,6 @@ class UnetEngine(NetEngine):
               d00.shape[-1], fp.grad_phys("conv0_0.bias").data_ptr(), aux=True)
         rec_wgrad(P, "conv0_0.wgrad", self.input(slot), d00, pc["conv0_0"], fp.grad_phys("conv0_0.weight"), aux=False)
         P.mark(0)
-        balance_wgrads(P, self.device)
         group_wgrads(P, self.device)
         slot.plans["bwd"] = P
         return P
@@ -1954,8 +1757,6 @@ class CUnetEngine(UnetEngine):
         # (the weight-gradient launch adds to a zeroed tensor; zeroed on the plan's stream, which the auxiliary queue follows)
         P.add("conv0_1.dwf.zero", lib.combat_memset_zero, self.dwf01.data_ptr(), self.dwf01.numel() * 4)
         rec_wgrad(P, "conv0_1.wgrad", slot.bufs["a.conv0_1"], d, self.pc["conv0_1"], self.dwf01)
-        if P.pending_reduces:        # (a deferred slab reduction: dwf01 must be final before it is copied)
-            P.flush_reduces()
         taps = slot.buf("cond.taps", (slot.N, 9, nf), f32)
         y = self.labels(slot)
         dw = self.fp.grad_phys("conv0_1.weight")

@@ -15,7 +15,6 @@ kernel launches with no host synchronisation; metric counters stay on the device
 """
 from __future__ import annotations
 
-import contextlib
 import copy
 import math
 from dataclasses import dataclass, field
@@ -31,8 +30,7 @@ from . import ops, trigger
 from ._lib import lib
 from .augment import PostTensorTransform
 from .dist import GradReducer, bucket_ranges
-from .engine import (FreqEngine, PlanSeq, PreActEngine, UnetEngine, _zero_grad_call, f32, low_priority_stream,
-                     short_workgroups)
+from .engine import FreqEngine, PlanSeq, PreActEngine, UnetEngine, _zero_grad_call, f32, short_workgroups
 
 BUCKETS = (8, 16, 32, 64, 128, 256, 512, 1024)
 
@@ -114,8 +112,8 @@ def order_tables(first: torch.Tensor, rest: torch.Tensor, num_bd: int):
 _STREAMS: Dict = {}
 
 
-def shared_stream(device, kind: str, priority: int = 0) -> torch.cuda.Stream:
-    """The process-wide stream of a kind ("main", "side") on a device.  Streams are NOT per step object: the HIP
+def shared_stream(device, kind: str) -> torch.cuda.Stream:
+    """The process-wide stream of a kind ("side") on a device.  Streams are NOT per step object: the HIP
     runtime multiplexes a process's streams onto a handful of hardware queues, and with the nine streams that two
     step objects with private streams add up to (bench.py's golden gate + the timed step) launches started to block on
     the host -- 10.6 instead of 4.3 ms/step, 9 ms of it inside the enqueue calls."""
@@ -123,23 +121,11 @@ def shared_stream(device, kind: str, priority: int = 0) -> torch.cuda.Stream:
     key = (dev.index if dev.index is not None else torch.cuda.current_device(), kind)
     s = _STREAMS.get(key)
     if s is None:
-        s = low_priority_stream(dev) if (kind != "main" and LOW_PRIO_SIDE) else torch.cuda.Stream(device=dev, priority=priority)
+        s = torch.cuda.Stream(device=dev)
         _STREAMS[key] = s
     return s
 
 
-LOW_PRIO_SIDE = os.environ.get("COMBAT_LOW_PRIO_SIDE", "0") == "1"   # experiment: second / auxiliary queues below the critical one
-
-SIDE_SHORT_WORKGROUPS = os.environ.get("COMBAT_SIDE_WS", "0") != "1"   # (COMBAT_SIDE_WS=1: A/B, the persistent kernel on the second stream too)
-# COMBAT_MERGE_C_EVAL=1 (A/B): netC's two eval-mode forwards of Phase G (train_generator.py:227-228) as ONE 2n-image
-# pass on the critical queue -- [aug(inputs) ; aug(inputs_bd)], backward on the second half -- as the clean model's
-# already are, instead of the metric-only half on the second stream.  Fewer, fatter launches against a longer critical chain.
-MERGE_C_EVAL = os.environ.get("COMBAT_MERGE_C_EVAL", "0") == "1"
-# COMBAT_FUSED_HEAD=1: one head launch per differentiated pass (combat_head_fwd_bwd) and the linear layer's weight gradient
-# beside the input-gradient chain.  OFF by default: two dependent launches and a 6.5-us bubble fewer on the critical queue
-# per pass, and the step did not move (3.765 / 3.762 against 3.735 / 3.742 ms on one box, 3.868 against 3.848 on another):
-# the step is bound by the CU-time of its heavy launches, not by the length of the critical queue's chain.
-FUSED_HEAD = os.environ.get("COMBAT_FUSED_HEAD", "0") == "1"
 FORCE_ALLREDUCE = os.environ.get("COMBAT_FORCE_ALLREDUCE", "0") == "1"   # issue the bucketed all-reduces even at world size 1
 #                                                                          (tests: RCCL's streams beside the step's on ONE GPU)
 
@@ -226,7 +212,6 @@ class AlternatedStep(PerBatchSize):
     TABLE = (5, 2, 7)   # augmentation tables, blur kernels (sigma_c, sigma_g) and label rows of the step table
     FIXED_BLUR = False   # True: the blur is the reference script's module-level GaussianBlur -- kernel 3, sigma in
     #                      (0.1, 1) -- whatever --kernel_size / --sigma say
-    CAN_MERGE_C = True   # COMBAT_MERGE_C_EVAL applies (to this class alone: the subclasses lay netC's eval passes out themselves)
 
     def __init__(self, netC, netG, clean_model, netF, opt, process_group=None):
         if self.FIXED_BLUR:
@@ -241,8 +226,6 @@ class AlternatedStep(PerBatchSize):
         self.netC, self.netG, self.clean_model, self.netF = netC, netG, clean_model, netF
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
-        if self.world > 1 or (FORCE_ALLREDUCE and process_group is not None):
-            self.eC.flush_at_marks = self.eG.flush_at_marks = True    # gradients above an all-reduce mark must be final there
         self.hw = opt.input_height
         dev = self.dev
         self.P = trigger.lowpass_matrix(self.hw, opt.ratio).to(dev)
@@ -251,7 +234,6 @@ class AlternatedStep(PerBatchSize):
         self.acc = torch.zeros(8, dtype=torch.float64, device=dev)  # running sums for logging
         self.acc_side = torch.zeros((), dtype=torch.float64, device=dev)   # detector hits (counted on the second stream)
         self._side = None
-        self._main = None
         self._host = None
         self.steps_done = 0
         self.samples = 0                 # images since the last metric reset
@@ -293,26 +275,22 @@ class AlternatedStep(PerBatchSize):
         lab = s.d_targets
         s.sC_train = eC.slot("C.train", n, hw)
         s.sC_train.bufs["targets"] = lab[LAB_TOTAL]
-        s.merge_c = MERGE_C_EVAL and self.CAN_MERGE_C
         self._c_eval_slots(s)
         s.sK_eval = eK.slot("K.eval2", 2 * n, hw)
         s.sK_eval.bufs["targets"], s.sK_eval.bufs["targets2"] = lab[LAB_K].view(-1), lab[LAB_K2].view(-1)
         s.sG = self._gen_slot(n)
         s.sF = self.eF.slot("F", n, hw) if self.eF is not None else None
         w_cm = float(self.opt.clean_model_weight)
-        # one head launch per differentiated pass (forward + feature gradient: combat_head_fwd_bwd), where the engine has it
-        hb = FUSED_HEAD and type(eC) is PreActEngine
         s.pl = dict(
-            C_train_f=eC.forward_plan(s.sC_train, True, **(dict(head_bwd=True) if hb else {})),
-            C_train_b=eC.backward_train_plan(s.sC_train, **(dict(head_done=True) if hb else {})),
-            C_eval_f=self._c_eval_fwd_plan(s, hb),
+            C_train_f=eC.forward_plan(s.sC_train, True),
+            C_train_b=eC.backward_train_plan(s.sC_train),
+            C_eval_f=self._c_eval_fwd_plan(s),
         )
         s.pl.update(self._gen_plans(s))
-        s.sC_bd, s.pl["C_bd_b"] = self._c_eval_bwd_plan(s, hb)
+        s.sC_bd, s.pl["C_bd_b"] = self._c_eval_bwd_plan(s)
         # the second stream's passes run beside the critical queue: one tile per workgroup (engine.short_workgroups)
-        with (short_workgroups() if SIDE_SHORT_WORKGROUPS else contextlib.nullcontext()):
-            if not s.merge_c:
-                s.pl["C_met_f"] = eC.forward_plan(s.sC_met, False, 1.0, False)
+        with short_workgroups():
+            s.pl["C_met_f"] = eC.forward_plan(s.sC_met, False, 1.0, False)
             s.pl["K_eval_f"] = eK.forward_plan(s.sK_eval, False, w_cm, True, split_head=True)
             s.sK_bd = s.sK_eval.half_view(n, n, eK.FWD_SHARED)
             s.pl["K_bd_b"] = eK.backward_eval_plan(s.sK_bd, w_cm)
@@ -323,32 +301,19 @@ class AlternatedStep(PerBatchSize):
     # ---- netC's eval-mode passes of Phase G (train_generator.py:227-231): slots with their labels, forward, input-gradient backward
     def _c_eval_slots(self, s) -> None:
         eC, hw, n, lab = self.eC, self.hw, s.n, s.d_targets
-        if s.merge_c:
-            s.sC_eval = eC.slot("C.eval2", 2 * n, hw)   # [metric half ; loss half]
-            s.sC_met = s.sC_eval
-            s.sC_eval.bufs["targets"] = lab[LAB_TARGETS:LAB_BD + 1].view(-1)
-        else:
-            s.sC_eval = eC.slot("C.evalbd", n, hw)      # netC on the triggered images: on the critical path, so on its own
-            s.sC_met = eC.slot("C.metric", n, hw)       # netC on the clean images (accuracy only): second stream
-            s.sC_eval.bufs["targets"], s.sC_met.bufs["targets"] = lab[LAB_BD], lab[LAB_TARGETS]
+        s.sC_eval = eC.slot("C.evalbd", n, hw)      # netC on the triggered images: on the critical path, so on its own
+        s.sC_met = eC.slot("C.metric", n, hw)       # netC on the clean images (accuracy only): second stream
+        s.sC_eval.bufs["targets"], s.sC_met.bufs["targets"] = lab[LAB_BD], lab[LAB_TARGETS]
 
-    def _c_eval_fwd_plan(self, s, hb):
-        return self.eC.forward_plan(s.sC_eval, False, 1.0, False,
-                                    **(dict(split_head=True) if s.merge_c else dict(head_bwd=True) if hb else {}))
+    def _c_eval_fwd_plan(self, s):
+        return self.eC.forward_plan(s.sC_eval, False, 1.0, False)
 
-    def _c_eval_bwd_plan(self, s, hb):
-        eC = self.eC
-        sbd = s.sC_eval.half_view(s.n, s.n, eC.FWD_SHARED) if s.merge_c else s.sC_eval
-        return sbd, eC.backward_eval_plan(sbd, 1.0, **(dict(head_done=True) if hb and not s.merge_c else {}))
+    def _c_eval_bwd_plan(self, s):
+        return s.sC_eval, self.eC.backward_eval_plan(s.sC_eval, 1.0)
 
     def _c_eval_inputs(self, x_ptr, bd_ptr, xC, aug_ptr, n, st) -> None:
-        """The augmented images of netC's differentiated eval pass (:228; merged: + :227)."""
-        hw = self.hw
-        if self.cur.merge_c:
-            ops.check(lib.combat_augment_fwd(x_ptr, None, aug_ptr[2], n, hw, xC.data_ptr(), None, st), "augment 2")
-            ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[3], n, hw, xC[n:].data_ptr(), None, st), "augment 3")
-        else:
-            ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[3], n, hw, xC.data_ptr(), None, st), "augment 3")
+        """The augmented images of netC's differentiated eval pass (:228)."""
+        ops.check(lib.combat_augment_fwd(bd_ptr, None, aug_ptr[3], n, self.hw, xC.data_ptr(), None, st), "augment 3")
 
     def _c_eval_grads(self, aug_ptr, n, st) -> None:
         """Image gradient of that pass through the augmentation -> d_bd."""
@@ -383,21 +348,8 @@ class AlternatedStep(PerBatchSize):
         as the DataLoader yields them (train_generator.py:170-171).
 
         The step runs on the caller's stream plus two process-wide ones (second stream, auxiliary weight-gradient
-        queue).  COMBAT_OWN_STREAM=1 moves the critical chain to a high-priority stream of its own (joined with the
-        caller's on both sides): 4.18 -> 4.15 ms/step on a quiet process, but the HIP runtime multiplexes a process's
-        streams onto few hardware queues and a high-priority stream makes that mapping fragile -- ONE more stream in
-        use anywhere in the process (a collective library's, a second step object's) and launches block on the host:
-        7-11 ms/step measured.  Without it the step tolerates four foreign streams (4.28-4.33 ms/step; 5.4 at six).
-        Off by default for that reason."""
-        if self.serial or os.environ.get("COMBAT_OWN_STREAM", "0") != "1":
-            return self._run(inputs, targets_cpu, rnd, lr_c, lr_g, prof)
-        caller = torch.cuda.current_stream()
-        if self._main is None:
-            self._main = shared_stream(self.dev, "main", priority=-1)
-        self._main.wait_stream(caller)
-        with torch.cuda.stream(self._main):
-            self._run(inputs, targets_cpu, rnd, lr_c, lr_g, prof)
-        caller.wait_stream(self._main)
+        queue); it tolerates four foreign streams in the process (4.28-4.33 ms/step; 5.4 at six: DESIGN.md section 5)."""
+        self._run(inputs, targets_cpu, rnd, lr_c, lr_g, prof)
 
     def _run(self, inputs, targets_cpu, rnd, lr_c, lr_g, prof) -> None:
         opt = self.opt
@@ -436,17 +388,11 @@ class AlternatedStep(PerBatchSize):
         extra = self.eG.small_refresh_copy() if hasattr(self.eG, "small_refresh_copy") else None
         direct = inputs.dtype == f32 and inputs.is_contiguous() and (inputs.is_cuda or inputs.is_pinned()) and \
             tuple(inputs.shape) == tuple(s.inputs.shape)
-        if os.environ.get("COMBAT_NO_COPY3") == "1":          # A/B: three asynchronous copies
-            s.tab.copy_(hs["raw"], non_blocking=True)
-            direct = False
-            if extra:
-                self.eG.bias8_taken = False
-        else:
-            ops.check(lib.combat_copy3(s.tab.data_ptr(), hs["raw"].data_ptr(), hs["raw"].numel(),
-                                       s.inputs.data_ptr() if direct else None, inputs.data_ptr() if direct else None,
-                                       inputs.numel() * 4 if direct else 0,
-                                       extra[0] if extra else None, extra[1] if extra else None, extra[2] if extra else 0, st),
-                      "combat_copy3")
+        ops.check(lib.combat_copy3(s.tab.data_ptr(), hs["raw"].data_ptr(), hs["raw"].numel(),
+                                   s.inputs.data_ptr() if direct else None, inputs.data_ptr() if direct else None,
+                                   inputs.numel() * 4 if direct else 0,
+                                   extra[0] if extra else None, extra[1] if extra else None, extra[2] if extra else 0, st),
+                  "combat_copy3")
         hs["done"] = torch.cuda.Event()
         hs["done"].record()
         # combat_copy3 reads a pinned host batch through its device mapping, which torch's caching host allocator cannot
@@ -484,7 +430,7 @@ class AlternatedStep(PerBatchSize):
         # before it reads the poisoned images and for `ev_side` before the generator backward.
         side = self._side_stream()
         side.wait_event(ev_fork)
-        xK, xC = eK.input(s.sK_eval), eC.input(s.sC_eval)     # [2n, ...]: metric half, loss half / [n, ...]: loss images
+        xK, xC = eK.input(s.sK_eval), eC.input(s.sC_eval)     # [2n, ...]: metric half, loss half / netC's loss images
         bd_ptr = s.bd.data_ptr()
         with torch.cuda.stream(side):
             s2 = side.cuda_stream
@@ -510,7 +456,7 @@ class AlternatedStep(PerBatchSize):
         # ================= Phase G (train_generator.py:216-255; generator forward and clean-model chain: above) =====
         torch.cuda.current_stream().wait_event(ev_bd)
         self._c_eval_inputs(x_ptr, bd_ptr, xC, aug_ptr, n, st)
-        pl["C_eval_f"].run(prof)               # :228, :231 (merged: + :227)
+        pl["C_eval_f"].run(prof)               # :228, :231
         # ---- everything that is only logged (:227 accuracy of the updated netC on the clean images, :245-247
         # detector, :234-243 L2 / gradient-L2 terms) is forked to the second stream HERE: underneath the surrogate's
         # input-gradient pass and the generator backward.  Measured on one box (ms/step): forked after the
@@ -522,10 +468,9 @@ class AlternatedStep(PerBatchSize):
         with torch.cuda.stream(side):
             side.wait_event(ev_late)
             s2 = side.cuda_stream
-            if not s.merge_c:
-                ops.check(lib.combat_augment_fwd(x_ptr, None, aug_ptr[2], n, hw, eC.input(s.sC_met).data_ptr(), None, s2),
-                          "augment 2")
-                pl["C_met_f"].run(prof)
+            ops.check(lib.combat_augment_fwd(x_ptr, None, aug_ptr[2], n, hw, eC.input(s.sC_met).data_ptr(), None, s2),
+                      "augment 2")
+            pl["C_met_f"].run(prof)
             if eF is not None:
                 ops.check(lib.combat_dct_u8(bd_ptr, self.D.data_ptr(), n, hw, eF.input(s.sF).data_ptr(), s2), "dct")
                 pl["F_f"].run(prof)
@@ -610,7 +555,7 @@ class AlternatedStep(PerBatchSize):
             out["loss_c_sum"] += float(cC["loss"])
             out["loss_ce_sum"] += float(cE["loss"])
             out["clean_model_loss_sum"] += float(kE["loss"]) / w_cm
-            out["clean_correct"] += int(sCm.bufs["correct0"][0]) if "correct0" in sCm.bufs else int(self.eC.head_bufs(sCm)["correct"][0])
+            out["clean_correct"] += int(self.eC.head_bufs(sCm)["correct"][0])
             out["bd_correct"] += int(cE["correct"][0])
             out["clean_model_correct"] += int(sKe.bufs["correct0"][0])
             out["clean_model_bd_ba"] += int(kE["correct"][0])
@@ -642,7 +587,6 @@ class WanetStep(AlternatedStep):
     blur is drawn (the reference's WaNet loop has none), so the torch RNG stream is consumed by the augmentation only."""
 
     WARP_GROUPS = 8     # image ranges of the warp backward (partial sums: deterministic, no atomics)
-    CAN_MERGE_C = False
 
     def __init__(self, netC, netG, clean_model, netF, opt, process_group=None):
         super().__init__(netC, netG, clean_model, netF, opt, process_group)
@@ -716,7 +660,6 @@ class InputAwareStep(AlternatedStep):
 
     TABLE = (6, 3, 9)   # + the cross images' augmentation table, the blur kernel of sigma_x, the LAB_CROSS rows
     FIXED_BLUR = True
-    CAN_MERGE_C = False
     _inputs2_src = None
 
     def run(self, inputs: torch.Tensor, targets_cpu: torch.Tensor, inputs2: torch.Tensor,
@@ -779,10 +722,10 @@ class InputAwareStep(AlternatedStep):
         s.sC_met = self.eC.slot("C.metric", s.n, self.hw)
         s.sC_eval.bufs["targets"], s.sC_met.bufs["targets"] = s.d_targets[LAB_CROSS].view(-1), s.d_targets[LAB_TARGETS]
 
-    def _c_eval_fwd_plan(self, s, hb):
+    def _c_eval_fwd_plan(self, s):
         return self.eC.forward_plan(s.sC_eval, False, 1.0, False, two_loss=True)
 
-    def _c_eval_bwd_plan(self, s, hb):
+    def _c_eval_bwd_plan(self, s):
         return s.sC_eval, self.eC.backward_eval_plan(s.sC_eval, 1.0, half_weights=(1.0, float(self.opt.cross_weight)))
 
     # ---- the step's pieces
@@ -905,7 +848,6 @@ class MultiLabelStep(AlternatedStep):
     ONE combat_trigger_groups_fwd / _bwd launch.  Single rank only."""
 
     FIXED_BLUR = True
-    CAN_MERGE_C = False
 
     def __init__(self, netC, netG, clean_model, netF, opt, process_group=None):
         if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
@@ -1022,7 +964,6 @@ class ImperceptibleStep(AlternatedStep):
     inputs_bd across the strips' seams; the launch count is the parent's there too."""
 
     FIXED_BLUR = True    # (the draws keep the parent's order: one sigma per create_inputs_bd call, :172-174 and :203)
-    CAN_MERGE_C = False
 
     def _build_set(self, n: int):
         s = super()._build_set(n)
@@ -1079,8 +1020,6 @@ class ClassifierStep(PerBatchSize):
             raise ValueError("ClassifierStep: unsupported generator %r (UnetGenerator or GridGenerator expected)" % type(netG).__name__)
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
-        if self.world > 1 or (FORCE_ALLREDUCE and process_group is not None):
-            self.eC.flush_at_marks = True
         self.hw = opt.input_height
         self.P = trigger.lowpass_matrix(self.hw, opt.ratio).to(self.dev)
         self.k1 = torch.zeros(3, dtype=f32, device=self.dev)
@@ -1096,9 +1035,8 @@ class ClassifierStep(PerBatchSize):
         s.tab_i = torch.zeros(2, n, dtype=torch.int32, device=dev)
         s.tab_f = torch.zeros(n, 4, dtype=f32, device=dev)
         s.slot = self.eC.slot("V.train", n, hw)
-        hb = FUSED_HEAD and type(self.eC) is PreActEngine
-        s.fwd = self.eC.forward_plan(s.slot, True, **(dict(head_bwd=True) if hb else {}))
-        s.bwd = self.eC.backward_train_plan(s.slot, **(dict(head_done=True) if hb else {}))
+        s.fwd = self.eC.forward_plan(s.slot, True)
+        s.bwd = self.eC.backward_train_plan(s.slot)
         return s
 
     def run(self, inputs: torch.Tensor, targets_cpu: torch.Tensor, poisoned_cpu: Optional[torch.Tensor] = None,

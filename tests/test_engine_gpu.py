@@ -549,63 +549,40 @@ def test_backward_plans_do_not_share_weight_gradient_scratch(mods):
         engine.Plan.default_aux_queues = 1
 
 
-def test_deferred_weight_gradient_reductions(mods):
-    """combat_wgrad_args.defer_reduce + combat_conv_wgrad_reduce + combat_plan_set_after (opt-in: COMBAT_DEFER_REDUCE=1;
-    measured slower on the step, see engine.Plan.defer_reduces): a training backward plan whose slab reductions run
-    on the plan's own stream, each behind its weight-gradient launch on the auxiliary queue, gives the gradients of
-    the default plan (reduction right behind each kernel) -- in C replay, Python replay and in line."""
-    nets, ops, engine = mods["nets"], mods["ops"], mods["engine"]
-    from combat_amd._lib import lib
-    gen = torch.Generator().manual_seed(4)
-    x = torch.rand(128, 3, 32, 32, generator=gen) * 2 - 1
-    t = torch.randint(0, 10, (128,), generator=gen)
-    m = seeded(nets.PreActResNet18, 0).cuda()
-    eng = m._net_engine()
-    eng.refresh()
-    names = [k for k, _ in m.named_parameters()]
-
-    def build(tag, defer):
-        engine.Plan.defer_reduces = defer
-        try:
-            slot = eng.slot(tag, 128, 32)
-            ops.image_to_c8(x.cuda(), eng.input(slot))
-            eng.head_bufs(slot)["targets"].copy_(t.cuda())
-            eng.forward_plan(slot, True).run()
-            return eng.backward_train_plan(slot)
-        finally:
-            engine.Plan.defer_reduces = False
-
-    def grads(run):
-        run()
-        torch.cuda.synchronize()
-        return {k: eng.fp.logical(eng.fp.grad, k).detach().float().cpu().clone() for k in names}
-
-    ref_plan, plan = build("defer.ref", False), build("defer.on", True)
-    engine.REDUCE_BEHIND = True          # opt-in (COMBAT_REDUCE_BEHIND=1): the reductions ride in the next weight gradient
+def test_plan_with_a_call_dependency_replays_alike_in_every_mode(mods):
+    """combat_plan_set_after / Call.after: CUnetEngine.backward_plan's cond.wgrad (auxiliary queue) waits for
+    conv0_1.wgrad, whose scratch it copies into the parameter's gradient rows.  The same plan gives the same flat
+    gradient in C replay, Python replay and in line -- bit for bit in deterministic mode (every reduction of the
+    plan in a fixed order)."""
+    nets, engine = mods["nets"], mods["engine"]
+    from test_multilabel_gpu import Opt as MultiLabelOpt, _run_engine
+    gen = torch.Generator().manual_seed(6)
+    x = torch.rand(3, 3, 32, 32, generator=gen) * 2 - 1
+    cot = torch.randn(3, 3, 32, 32, generator=gen)
+    m = seeded(lambda: nets.CUnetGeneratorv1(MultiLabelOpt()), 5).cuda()
+    was = engine.deterministic()
+    engine.set_deterministic(True)
     try:
-        behind = build("defer.behind", False)
+        _, slot, eng = _run_engine(mods, m, x, torch.tensor([0, 9, 4]), cot)
+        plan = eng.backward_plan(slot)
+        waits = [c for c in plan.calls if c.after is not None]
+        assert [c.what for c in waits] == ["cond.wgrad"] and waits[0].queue is not None
+        assert "conv0_1.wgrad" in waits[0].after.what
+        got = {}
+        for mode in ("c", "py", "serial"):
+            engine.Plan.compiled, engine.Plan.serial = mode != "py", mode == "serial"
+            try:
+                plan.run()
+            finally:
+                engine.Plan.compiled, engine.Plan.serial = True, False
+            torch.cuda.synchronize()
+            got[mode] = eng.fp.grad.clone()
     finally:
-        engine.REDUCE_BEHIND = False
-    n_red = sum(1 for c in plan.calls if c.func is lib.combat_conv_wgrad_reduce)
-    assert n_red >= 12 and sum(1 for c in plan.calls if c.after is not None) == n_red
-    assert not any(c.func is lib.combat_conv_wgrad_reduce for c in ref_plan.calls)
-    # reduce-behind (round 4, opt-in): the slab-leaving launches form ONE chain per plan -- each carries its
-    # predecessor (reduce_first), only the last one gets a reduction call
-    chained = [a for a in behind.wgrads if a.defer_reduce]
-    assert len(chained) == n_red and sum(1 for a in chained if a.reduce_first) == n_red - 1
-    assert sum(1 for c in behind.calls if c.func is lib.combat_conv_wgrad_reduce) == 1
-    ref = grads(ref_plan.run)
-    first = grads(behind.run)
-    for k in names:
-        assert rel_l2(first[k], ref[k]) < 1e-5, ("reduce-behind", k, rel_l2(first[k], ref[k]))
-    for mode in ("c", "py", "serial"):
-        engine.Plan.compiled, engine.Plan.serial = mode != "py", mode == "serial"
-        try:
-            got = grads(plan.run)
-        finally:
-            engine.Plan.compiled, engine.Plan.serial = True, False
-        for k in names:
-            assert rel_l2(got[k], ref[k]) < 1e-5, (mode, k, rel_l2(got[k], ref[k]))
+        engine.set_deterministic(was)
+    lo, n, _ = eng.fp.offsets["conv0_1.weight"]
+    assert float(got["c"][lo:lo + n].abs().max()) > 0.0 and float(got["c"].abs().max()) > 0.0
+    for mode in ("py", "serial"):
+        assert torch.equal(got[mode], got["c"]), (mode, rel_l2(got[mode], got["c"]))
 
 
 def test_plan_replay_in_c_equals_python_replay(mods):
@@ -904,59 +881,11 @@ def test_alternated_step_runs_with_sampled_randomness_and_empty_poison(mods):
     assert st2._side is st._side and st._side is not None
 
 
-def test_preact_train_forward_with_lds_prologue_equals_the_chain(mods):
-    """COMBAT_FUSED_PROLOGUE=1 (engine.FUSED_PROLOGUE): PreActResNet18's train forward with relu(bn(.)) applied in LDS
-    by the consuming convolutions (conv3x3_dma_pro_kernel + combat_norm_finalize) against the default chain
-    (combat_norm_act_fused + prologue-free convolution).  At B = 128 both run the same tiles on every layer (the
-    weight-stationary kernel of the chain's 64-channel layers is bit-identical to the ring tile), so every stored
-    tensor of the forward -- raw outputs, activated tensors, statistics, running statistics, loss -- is BIT-identical
-    (both modes recorded with the ring tiles: the persistent kernel groups its statistics rows per workgroup);
-    the backward reads the same tensors (gradient: fp32-atomic noise of a few weight-gradient launches only).  The
-    opt-in path is slower (engine.py) and stays off; this keeps it correct."""
-    engine, nets = mods["engine"], mods["nets"]
-    b = 128
-    res = {}
-    prev = engine.FUSED_PROLOGUE
-    try:
-        for fused in (False, True):
-            engine.FUSED_PROLOGUE = fused
-            net = seeded(nets.PreActResNet18, 0).cuda()
-            eng = net._net_engine()
-            eng.refresh()
-            slot = eng.slot("pro.%d" % fused, b, 32)
-            x, t = bench_batch(0)
-            ops_ = mods["ops"]
-            xd = x.cuda()
-            ops_.image_to_c8(xd, eng.input(slot))
-            eng.head_bufs(slot)["targets"].copy_(t)
-            with engine.short_workgroups():       # (ring tiles in both modes: the persistent kernel groups its statistics rows differently)
-                fwd, bwd = eng.forward_plan(slot, True), eng.backward_train_plan(slot)
-            names = [c.what for c in fwd.calls]
-            assert any(w.endswith(".finalize") for w in names) == fused
-            assert sum(w.endswith(".finact") for w in names) == (3 if fused else 16)      # the stride-2 blocks' inputs stay materialised
-            fwd.run()
-            bwd.run()
-            torch.cuda.synchronize()
-            res[fused] = ({k: v.clone() for k, v in slot.bufs.items() if not k.startswith("g.")}, eng.fp.grad.clone(),
-                          {k: v.detach().clone() for k, v in net.state_dict().items() if "running" in k or "num_batches" in k})
-    finally:
-        engine.FUSED_PROLOGUE = prev
-    (ba, ga, ra), (bb, gb, rb_) = res[False], res[True]
-    for k in sorted(ba):
-        if k == "loss":      # (summed over samples with an fp32 atomic: last-bit noise between any two runs)
-            assert abs(float(ba[k]) - float(bb[k])) < 1e-5
-        elif k in bb and ba[k].shape == bb[k].shape and not k.endswith(".part"):     # (row counts differ: one row per persistent workgroup / per tile)
-            assert torch.equal(ba[k], bb[k]), k
-    for k in ra:
-        assert torch.equal(ra[k], rb_[k]), k
-    assert rel_l2(gb, ga) < 1e-5
-
-
 def test_fused_head_plans_equal_the_two_launch_plans(mods):
-    """PreActEngine.forward_plan(head_bwd=True) + backward_*_plan(head_done=True) (COMBAT_FUSED_HEAD=1 in the steps): the head's
-    forward and feature gradient as one launch, the linear layer's weight gradient on the auxiliary queue -- the feature
-    gradient bit-identical, parameter gradients equal up to the atomic sums of a few weight-gradient launches, the
-    image gradient of the eval pass bit-identical."""
+    """PreActEngine.forward_plan(eval, head_bwd=True) + backward_eval_plan(head_done=True), the defenses' path (Neural
+    Cleanse, Grad-CAM): the head's forward and feature gradient as one launch -- the feature gradient and the image
+    gradient bit-identical to the two-launch plans', the loss equal up to its atomic sum.  A train-mode pass has no
+    backward that starts behind the head: asking for one is refused."""
     nets, ops_ = mods["nets"], mods["ops"]
     net = seeded(nets.PreActResNet18, 0).cuda()
     eng = net._net_engine()
@@ -964,62 +893,20 @@ def test_fused_head_plans_equal_the_two_launch_plans(mods):
     x, t = bench_batch(0, bs=32)
     out = {}
     for fused in (False, True):
-        slot = eng.slot("head.%d" % fused, 32, 32)
+        slot = eng.slot("head.e%d" % fused, 32, 32)
         ops_.image_to_c8(x.cuda(), eng.input(slot))
         eng.head_bufs(slot)["targets"].copy_(t)
         kw_f, kw_b = (dict(head_bwd=True), dict(head_done=True)) if fused else ({}, {})
-        fwd, bwd = eng.forward_plan(slot, True, **kw_f), eng.backward_train_plan(slot, **kw_b)
-        assert sum("head" in c.what for c in fwd.calls) == 1 and any(c.what == "head_bwd.w" for c in bwd.calls) == fused
+        fwd, bwd = eng.forward_plan(slot, False, 1.0, False, **kw_f), eng.backward_eval_plan(slot, 1.0, **kw_b)
+        assert sum("head" in c.what for c in fwd.calls) == 1 and any(c.what == "head_bwd" for c in bwd.calls) != fused
         fwd.run()
         bwd.run()
         torch.cuda.synchronize()
-        res = [slot.bufs["g.feat"].clone(), eng.fp.grad.clone(), float(eng.head_bufs(slot)["loss"])]
-        eslot = eng.slot("head.e%d" % fused, 32, 32)
-        ops_.image_to_c8(x.cuda(), eng.input(eslot))
-        eng.head_bufs(eslot)["targets"].copy_(t)
-        eng.forward_plan(eslot, False, 1.0, False, **kw_f).run()
-        eng.backward_eval_plan(eslot, 1.0, **kw_b).run()
-        torch.cuda.synchronize()
-        out[fused] = res + [eslot.bufs["g.img"].clone()]
-    assert torch.equal(out[False][0], out[True][0]) and torch.equal(out[False][3], out[True][3])
-    assert rel_l2(out[True][1], out[False][1]) < 1e-5 and abs(out[True][2] - out[False][2]) < 1e-5
-
-
-@pytest.mark.parametrize("switch", ["merge_c_eval", "fused_head", "reduce_behind", "fused_prologue"])
-def test_step_ab_switches_keep_the_results(mods, switch):
-    """Round 4's opt-in forms of the step (all measured no faster; kept selectable): netC's two Phase-G
-    eval forwards as one 2n pass (COMBAT_MERGE_C_EVAL), one head launch per differentiated pass (COMBAT_FUSED_HEAD),
-    weight-gradient reductions carried by the next launch (COMBAT_REDUCE_BEHIND), BatchNorm + ReLU in the consuming
-    convolution's LDS (COMBAT_FUSED_PROLOGUE).  Each must leave a step's losses, counters and updated weights where the
-    default leaves them (up to the summation order of the kernels it swaps)."""
-    step_mod, engine = mods["step"], mods["engine"]
-    gen = torch.Generator().manual_seed(11)
-    x = (torch.randint(0, 256, (32, 3, 32, 32), generator=gen).float() / 255 - 0.5) / 0.5
-    t = torch.randint(0, 10, (32,), generator=gen)
-    t[:5] = 0
-    flags = {"merge_c_eval": (step_mod, "MERGE_C_EVAL"), "fused_head": (step_mod, "FUSED_HEAD"),
-             "reduce_behind": (engine, "REDUCE_BEHIND"), "fused_prologue": (engine, "FUSED_PROLOGUE")}
-    mod, name = flags[switch]
-    out = []
-    for on in (False, True):
-        prev = getattr(mod, name)
-        setattr(mod, name, on)
-        try:
-            netc, clean, netg, netf = _build(mods, [0, 1, 2, 3])
-            st = step_mod.AlternatedStep(netc.cuda(), netg.cuda(), clean.cuda().eval(), netf.cuda().eval(), Opt())
-            for i in range(2):
-                st.run(x.cuda(), t, step_mod.StepRandomness(3, 0.4, 0.7, [None] * 5))
-            torch.cuda.synchronize()
-            out.append((st.read_metrics(), torch.cat([p.detach().flatten() for p in netc.parameters()]).clone(),
-                        torch.cat([p.detach().flatten() for p in netg.parameters()]).clone()))
-        finally:
-            setattr(mod, name, prev)
-    (m0, c0, g0), (m1, c1, g1) = out
-    for k in ("loss_c_sum", "loss_ce_sum", "clean_model_loss_sum", "loss_l2_sum"):
-        assert abs(m0[k] - m1[k]) <= 2e-3 * max(1.0, abs(m0[k])), (switch, k, m0[k], m1[k])
-    for k in ("clean_correct", "bd_correct", "clean_model_correct", "clean_model_bd_ba", "clean_model_bd_asr", "train_correct"):
-        assert abs(m0[k] - m1[k]) <= 1, (switch, k, m0[k], m1[k])
-    assert rel_l2(c1, c0) < 2e-3 and rel_l2(g1, g0) < 2e-3, (switch, rel_l2(c1, c0), rel_l2(g1, g0))
+        out[fused] = [slot.bufs["g.feat"].clone(), slot.bufs["g.img"].clone(), float(eng.head_bufs(slot)["loss"])]
+    assert torch.equal(out[False][0], out[True][0]) and torch.equal(out[False][1], out[True][1])
+    assert abs(out[True][2] - out[False][2]) < 1e-5
+    with pytest.raises(ValueError):
+        eng.forward_plan(eng.slot("head.t", 32, 32), True, head_bwd=True)
 
 
 def test_step_keeps_a_dropped_pinned_batch_alive(mods):

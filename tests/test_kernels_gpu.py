@@ -881,7 +881,7 @@ def test_wgrad_reduction_rides_in_the_next_weight_gradient(ops):
     reduction launch.  The carried reduction has a fixed summation order and no atomics, so (1) every dw of the chain
     equals the same layer launched alone with its own reduction launch up to summation order, (2) a second chain run
     reproduces the first BIT for bit, (3) a launch that cannot take its predecessor along (generic kernel) reduces it
-    first.  (Opt-in in the engines -- COMBAT_REDUCE_BEHIND=1 -- because it measured slower: engine.py.)"""
+    first.  (A library feature only: the engines do not record such chains, because they measured slower -- DESIGN.md section 5.)"""
     import ctypes
     from combat_amd._lib import WgradArgs, lib
     st = torch.cuda.current_stream().cuda_stream

@@ -15,7 +15,7 @@ MARK_BLOCKS = (6, 4, 2)     # an all-reduce mark follows the backward of these b
 @pytest.fixture(scope="module")
 def net():
     """One PreActResNet18, one batch, and per grouping mode a slot whose train forward has run and whose backward plan
-    is built (build(mode, flush_at_marks=False) -> (slot, plan)); deterministic mode for the module."""
+    is built (build(mode) -> (slot, plan)); deterministic mode for the module."""
     from combat_amd import engine, nets, ops
     from combat_amd._lib import lib
     before = lib.combat_get_deterministic()
@@ -29,21 +29,19 @@ def net():
     t = torch.randint(0, 10, (N,), generator=gen).cuda()
     built = {}
 
-    def build(mode, flush=False):
-        if (mode, flush) not in built:
-            saved, saved_flush = engine.Plan.wgrad_groups, eng.flush_at_marks
+    def build(mode):
+        if mode not in built:
+            saved = engine.Plan.wgrad_groups
             engine.Plan.wgrad_groups = mode
-            eng.flush_at_marks = flush
             try:
-                slot = eng.slot("group.%s.%d" % (mode, flush), N, 32)
+                slot = eng.slot("group.%s" % mode, N, 32)
                 ops.image_to_c8(x, eng.input(slot))
                 eng.head_bufs(slot)["targets"].copy_(t)
                 eng.forward_plan(slot, True).run()
-                built[(mode, flush)] = (slot, eng.backward_train_plan(slot))
+                built[mode] = (slot, eng.backward_train_plan(slot))
             finally:
                 engine.Plan.wgrad_groups = saved
-                eng.flush_at_marks = saved_flush
-        return built[(mode, flush)]
+        return built[mode]
 
     yield dict(engine=engine, lib=lib, eng=eng, build=build)
     lib.combat_set_deterministic(before)
@@ -113,12 +111,12 @@ def test_profiled_replay_lists_every_weight_gradient(net):
 
 
 def test_no_group_spans_an_all_reduce_mark(net):
-    """Data parallel (flush_at_marks): the gradients above a mark are final there, so every member of a group lies
-    in the stage its group call is recorded in -- read off the recorded plan, no second rank needed."""
+    """Data parallel: the gradients above a mark are final there, so every member of a group lies in the stage its
+    group call is recorded in -- read off the recorded plan, no second rank needed."""
     lib, eng = net["lib"], net["eng"]
-    _, off = net["build"]("off", True)
-    _, on = net["build"]("stages", True)
-    assert on.flush_at_marks and len(on.mark_offsets) == len(off.mark_offsets) == len(MARK_BLOCKS) + 1
+    _, off = net["build"]("off")
+    _, on = net["build"]("stages")
+    assert len(on.mark_offsets) == len(off.mark_offsets) == len(MARK_BLOCKS) + 1
     where = {c.what: i for i, c in enumerate(off.calls)}
     stage = lambda plan, i: sum(1 for c in plan.calls[:i] if c.mark is not None)
     groups = groups_of(lib, on)
