@@ -732,6 +732,62 @@ extern "C" int combat_maxpool2(const void *x, int32_t n, int32_t h, int32_t w, i
     return COMBAT_OK;
 }
 
+namespace {
+// Gradient of relu -> 2x2 max pool at the pool's input `a` (the post-ReLU tensor): each pooled gradient goes to the
+// window's first maximum in the scan order (0,0), (0,1), (1,0), (1,1) -- a strict `>` scan, nn.MaxPool2d's rule -- and
+// only where that maximum is positive (the ReLU's gradient is 0 at 0).  One thread: one window x 8 channels, four
+// 16-byte loads of `a`, one of the gradient, four 16-byte stores: every element of d_a is written exactly once.
+__global__ __launch_bounds__(256) void maxpool2_relu_bwd_kernel(const __bf16 *__restrict__ a, const __bf16 *__restrict__ g,
+                                                                int n, int h, int w, int C, __bf16 *__restrict__ d_a) {
+    const int nch = C >> 3, ho = h >> 1, wo = w >> 1;
+    const long total = (long)n * ho * wo * nch;
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+        const int ch = (int)(t % nch);
+        long p = t / nch;
+        const int ox = (int)(p % wo);
+        p /= wo;
+        const int oy = (int)(p % ho);
+        const long img = p / ho;
+        float v[4][8], gv[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            unpack8(*reinterpret_cast<const uint4 *>(a + ((img * h + 2 * oy + (k >> 1)) * w + 2 * ox + (k & 1)) * C + ch * 8), v[k]);
+        unpack8(*reinterpret_cast<const uint4 *>(g + ((img * ho + oy) * wo + ox) * C + ch * 8), gv);
+        int arg[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float m = v[0][e];
+            int am = 0;
+#pragma unroll
+            for (int k = 1; k < 4; ++k)
+                if (v[k][e] > m) {
+                    m = v[k][e];
+                    am = k;
+                }
+            arg[e] = m > 0.f ? am : -1;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float o[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = arg[e] == k ? gv[e] : 0.f;
+            *reinterpret_cast<uint4 *>(d_a + ((img * h + 2 * oy + (k >> 1)) * w + 2 * ox + (k & 1)) * C + ch * 8) = pack8(o);
+        }
+    }
+}
+}  // namespace
+
+extern "C" int combat_maxpool2_relu_bwd(const void *a, const void *d_pooled, int32_t n, int32_t h, int32_t w, int32_t C,
+                                        void *d_a, void *stream) {
+    COMBAT_PLAN_HOOK(combat_maxpool2_relu_bwd, a, d_pooled, n, h, w, C, d_a);
+    if (!a || !d_pooled || !d_a || n <= 0 || h <= 0 || w <= 0 || (h & 1) || (w & 1) || C <= 0 || (C & 7)) return COMBAT_EINVAL;
+    COMBAT_LAUNCH(maxpool2_relu_bwd_kernel, dim3(grid_for((long)n * (h / 2) * (w / 2) * (C / 8))), dim3(256), 0,
+                       as_stream(stream), reinterpret_cast<const __bf16 *>(a), reinterpret_cast<const __bf16 *>(d_pooled), n, h,
+                       w, C, reinterpret_cast<__bf16 *>(d_a));
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
+
 extern "C" int combat_elu_affine(const void *x, int64_t rows, int32_t C, const float *scale, const float *shift,
                                  void *out, void *stream) {
     COMBAT_PLAN_HOOK(combat_elu_affine, x, rows, C, scale, shift, out);

@@ -262,7 +262,148 @@ int launch_head_bwd_w(const float *dlogits, const float *pooled, int n, int in, 
     return COMBAT_OK;
 }
 
+// ---- flat head: view(n, -1) -> Linear -> CrossEntropyLoss over a 1 x 1 or 2 x 2 feature map (classifier_models/vgg.py:25-29,
+// :23; the final AvgPool2d(1, 1) of :44 is the identity).  No pooling: the Linear's column of feature (y, x, c) is torch's
+// NCHW flatten c * hw * hw + y * hw + x.
+constexpr int kFlatMaxIn = 2048;   // 512 channels x 2 x 2
+
+struct FlatHeadArgs {
+    const __bf16 *feat;
+    int hw, C, classes, n;
+    const float *W, *b;
+    const int64_t *targets;
+    float loss_weight;
+    float *logits, *dlogits, *loss_sum;
+    int *correct;
+    float *loss_part;   // as HeadFwdArgs::loss_part
+};
+
+__global__ __launch_bounds__(256) void flat_head_fwd_kernel(const FlatHeadArgs a) {
+    __shared__ __attribute__((aligned(16))) float sm[kFlatMaxIn];   // the image's features in the Linear's column order
+    __shared__ float lg[kMaxClasses];
+    const int tid = threadIdx.x, img = blockIdx.x;
+    const int px = a.hw * a.hw, in = a.C * px;
+    for (int i = tid; i < in; i += 256) {     // i = p * C + c: coalesced reads of the NHWC map
+        const int p = i / a.C, c = i - p * a.C;
+        sm[c * px + p] = (float)a.feat[(long)img * in + i];
+    }
+    __syncthreads();
+    {
+        const int lane = tid & 63, wv = tid >> 6;
+        for (int j = wv; j < a.classes; j += 4) {
+            float s = 0.f;
+            for (int i = lane; i < in; i += 64) s = fmaf(sm[i], a.W[(long)j * in + i], s);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            if (lane == 0) {
+                lg[j] = s + a.b[j];
+                a.logits[(long)img * a.classes + j] = lg[j];
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0 && a.targets) {
+        float mx = lg[0];
+        int am = 0;
+        for (int j = 1; j < a.classes; ++j)
+            if (lg[j] > mx) {
+                mx = lg[j];
+                am = j;
+            }
+        float se = 0.f;
+        for (int j = 0; j < a.classes; ++j) se += expf(lg[j] - mx);
+        const int t = (int)a.targets[img];
+        const float li = logf(se) + mx - lg[t];
+        if (a.loss_part) a.loss_part[img] = a.loss_weight * li / (float)a.n;
+        else if (a.loss_sum) atomicAdd(a.loss_sum, a.loss_weight * li / (float)a.n);
+        if (a.correct && am == t) atomicAdd(a.correct, 1);
+        if (a.dlogits)
+            for (int j = 0; j < a.classes; ++j)       // (head_bwd_feat_kernel's expression)
+                a.dlogits[(long)img * a.classes + j] =
+                    a.loss_weight / (float)a.n * (expf(lg[j] - mx) / se - (j == t ? 1.f : 0.f));
+    }
+}
+
+// Blocks [0, feat_blocks): d_feat[s][p][c] = bf16(sum_j dlogits[s][j] * W[j][c * px + p]), one thread per pixel x 8 channels.
+// The blocks behind them: dW[j][c * px + p] = sum_s dlogits[s][j] * feat[s][p][c] and db[j] = sum_s dlogits[s][j], one
+// thread per element, the images in index order in every mode (no atomics, no partial sums to meet).
+__global__ __launch_bounds__(256) void flat_head_bwd_kernel(const __bf16 *__restrict__ feat, int n, int hw, int C, int classes,
+                                                            const float *__restrict__ W, const float *__restrict__ dlogits,
+                                                            __bf16 *__restrict__ d_feat, float *__restrict__ dW,
+                                                            float *__restrict__ db, int feat_blocks) {
+    const int px = hw * hw, in = C * px;
+    if ((int)blockIdx.x < feat_blocks) {
+        const int nch = C >> 3;
+        const long t = (long)blockIdx.x * 256 + threadIdx.x;
+        if (t >= (long)n * px * nch) return;
+        const int ch = (int)(t % nch) * 8;
+        const long sp = t / nch;
+        const int p = (int)(sp % px);
+        const long img = sp / px;
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = 0.f;
+        for (int j = 0; j < classes; ++j) {
+            const float d = dlogits[img * classes + j];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = fmaf(d, W[(long)j * in + (ch + e) * px + p], o[e]);
+        }
+        *reinterpret_cast<uint4 *>(d_feat + (img * px + p) * C + ch) = pack8(o);
+        return;
+    }
+    const long e = (long)(blockIdx.x - feat_blocks) * 256 + threadIdx.x;
+    const long nw = (long)classes * in;
+    if (e < nw) {
+        const int j = (int)(e / in), i = (int)(e - (long)j * in);   // i = p * C + c: coalesced reads of the features
+        const int p = i / C, c = i - p * C;
+        float s = 0.f;
+        for (int smp = 0; smp < n; ++smp) s = fmaf(dlogits[(long)smp * classes + j], (float)feat[(long)smp * in + i], s);
+        dW[(long)j * in + c * px + p] = s;
+    } else if (e < nw + classes) {
+        const int j = (int)(e - nw);
+        float s = 0.f;
+        for (int smp = 0; smp < n; ++smp) s += dlogits[(long)smp * classes + j];
+        db[j] = s;
+    }
+}
+
+bool flat_head_shape_ok(int n, int hw, int C, int classes) {
+    return n > 0 && (hw == 1 || hw == 2) && C > 0 && !(C & 7) && C * hw * hw <= kFlatMaxIn && classes > 0 && classes <= kMaxClasses;
+}
+
 }  // namespace
+
+extern "C" int combat_flat_head_fwd(const void *feat, int32_t n, int32_t hw, int32_t C, const float *W, const float *b,
+                                    int32_t classes, const int64_t *targets, float loss_weight, float *logits,
+                                    float *dlogits, float *loss_sum, int32_t *correct, void *stream) {
+    COMBAT_PLAN_HOOK(combat_flat_head_fwd, feat, n, hw, C, W, b, classes, targets, loss_weight, logits, dlogits, loss_sum, correct);
+    if (!feat || !W || !b || !logits || !flat_head_shape_ok(n, hw, C, classes)) return COMBAT_EINVAL;
+    if (!targets && (dlogits || loss_sum || correct)) return COMBAT_EINVAL;
+    FlatHeadArgs a{reinterpret_cast<const __bf16 *>(feat), hw, C, classes, n, W, b, targets, loss_weight, logits, dlogits,
+                   loss_sum, correct, head_loss_part(loss_sum, targets, n, stream)};
+    COMBAT_LAUNCH(flat_head_fwd_kernel, dim3(n), dim3(256), 0, as_stream(stream), a);
+    CB_LAUNCH_CHECK();
+    if (a.loss_part) {
+        COMBAT_LAUNCH(head_loss_finish_kernel, dim3(1), dim3(1), 0, as_stream(stream), (const float *)a.loss_part, n, loss_sum);
+        CB_LAUNCH_CHECK();
+    }
+    return COMBAT_OK;
+}
+
+extern "C" int combat_flat_head_bwd(const void *feat, int32_t n, int32_t hw, int32_t C, const float *W, int32_t classes,
+                                    const float *dlogits, void *d_feat, float *dW, float *db, void *stream) {
+    COMBAT_PLAN_HOOK(combat_flat_head_bwd, feat, n, hw, C, W, classes, dlogits, d_feat, dW, db);
+    if (!W || !dlogits || !flat_head_shape_ok(n, hw, C, classes)) return COMBAT_EINVAL;
+    if ((dW == nullptr) != (db == nullptr) || (dW && !feat) || (!dW && !d_feat)) return COMBAT_EINVAL;
+    const int in = C * hw * hw;
+    const int feat_blocks = d_feat ? (int)(((long)n * hw * hw * (C / 8) + 255) / 256) : 0;
+    const int w_blocks = dW ? (int)(((long)classes * in + classes + 255) / 256) : 0;
+    COMBAT_LAUNCH(flat_head_bwd_kernel, dim3(feat_blocks + w_blocks), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const __bf16 *>(feat), n, hw, C, classes, W, dlogits, reinterpret_cast<__bf16 *>(d_feat), dW,
+                       db, feat_blocks);
+    CB_LAUNCH_CHECK();
+    return COMBAT_OK;
+}
 
 extern "C" int combat_head_fwd(const void *feat, int32_t n, int32_t hw, int32_t C, const float *W, const float *b,
                                int32_t classes, const int64_t *targets, float loss_weight, float *pooled,

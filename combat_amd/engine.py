@@ -1459,6 +1459,142 @@ class ResNetEngine(PreActEngine):
         return P
 
 
+class VggEngine(NetEngine):
+    """VGG13 (classifier_models/vgg.py:18-45) as a VICTIM: train-mode forward + parameter gradients (ClassifierStep) and
+    the eval-mode forward.  Five stages of two conv(3x3, bias) -> BatchNorm -> ReLU layers, a 2x2 max-pool behind each
+    stage, view + Linear + cross-entropy on the 1 x 1 (32 x 32 inputs) or 2 x 2 (64 x 64) map that is left.
+
+    The convolution bias is the launch's own epilogue term in both modes: the stored tensor and its batch statistics
+    include it, so running_mean is mean(conv) + b with no launch added, and an eval pass needs no fold of its own.  Its
+    gradient is mathematically zero under a train-mode BatchNorm (the norm's backward output sums to zero per channel):
+    no launch writes it and the zeroed gradient buffer keeps exact zeros there.
+    Tensors (layer l = 0..9): 'l%d.y' raw conv output (train), 'l%d.a' = relu(bn(.)), 'l%d.p' the pooled tensor behind
+    the odd layers.  There is no input-gradient plan: VGG13 as the generator's surrogate is out of scope."""
+
+    def __init__(self, module):
+        if getattr(module, "vgg_name", None) != "VGG13":
+            raise NotImplementedError("only VGG13 of the VGG table has a HIP engine, not %r" % getattr(module, "vgg_name", None))
+        super().__init__(module)
+        m = module
+        self.classes = m.classifier.out_features
+        self.layers: List[_Blk] = []
+        self.bns: List[_BN] = []
+        idx, cin = 0, 8
+        for widths in ((64, 64), (128, 128), (256, 256), (512, 512), (512, 512)):
+            for j, width in enumerate(widths):
+                conv, bn = m.features[idx], m.features[idx + 1]
+                assert conv.out_channels == width and isinstance(bn, torch.nn.BatchNorm2d)
+                e = _Blk()
+                e.prefix, e.width, e.pool = "features.%d" % idx, width, j == len(widths) - 1
+                e.pc = self._pc(conv.weight.data, 1, 1, cin, dup=not self.layers, need_dgrad=bool(self.layers))
+                e.bias = conv.bias.data
+                e.bn = _BN(self, bn, "features.%d" % (idx + 1))
+                self.layers.append(e)
+                self.bns.append(e.bn)
+                idx, cin = idx + 3, width
+            idx += 1     # the stage's MaxPool2d
+        self.lin_w, self.lin_b = m.classifier.weight.data, m.classifier.bias.data
+
+    fold_bn = PreActEngine.fold_bn
+    input = PreActEngine.input
+    head_bufs = PreActEngine.head_bufs
+
+    def _refresh_extra(self):
+        self.fold_bn()
+
+    def forward_plan(self, slot: Slot, train: bool, loss_weight: float = 1.0, with_targets2: bool = False,
+                     split_head: bool = False, head_bwd: bool = False, two_loss: bool = False, keep_raw_blocks=()) -> Plan:
+        """PreActEngine.forward_plan's argument list, so that a step written for the surrogates gets a message and not a
+        TypeError: every form beyond the plain pass belongs to a generator step or a defense and is refused."""
+        if with_targets2 or split_head or head_bwd or two_loss or tuple(keep_raw_blocks):
+            raise NotImplementedError("VGG13 is victim-only on the HIP path: its forward plan has no second-label counter, "
+                                      "split / two-loss head, head gradient or raw taps (DESIGN.md section 16)")
+        key = "fwd.%s.%g" % ("train" if train else "eval", loss_weight)
+        if key in slot.plans:
+            return slot.plans[key]
+        P = Plan("vgg." + key)
+        n, s = slot.N, slot.hw
+        cur = self.input(slot)
+        for li, e in enumerate(self.layers):
+            act = slot.buf("l%d.a" % li, (n, s, s, e.width))
+            if train:
+                y = slot.buf("l%d.y" % li, act.shape)
+                self._conv_norm(P, slot, e.bn.prefix, cur, y, e.pc, groups=1, gamma=e.bn.gamma, beta=e.bn.beta,
+                                running=(e.bn.rm, e.bn.rv, e.bn.nbt), act_dst=act, bias=e.bias)
+            else:
+                rec_conv(P, "l%d" % li, cur, None, e.pc, 0, bias=e.bias, act_dst=act, act=e.bn.eval_affine())
+            cur = act
+            if e.pool:
+                pooled = slot.buf("l%d.p" % li, (n, s // 2, s // 2, e.width))
+                P.hold(cur, pooled)
+                P.add("l%d.pool" % li, lib.combat_maxpool2, cur.data_ptr(), n, s, s, e.width, pooled.data_ptr())
+                cur, s = pooled, s // 2
+        h = self.head_bufs(slot)
+        P.hold(h, cur)
+        P.add("head", lib.combat_flat_head_fwd, cur.data_ptr(), n, s, cur.shape[-1], self.lin_w.data_ptr(),
+              self.lin_b.data_ptr(), self.classes, h["targets"].data_ptr(), loss_weight, h["logits"].data_ptr(),
+              h["dlogits"].data_ptr(), h["loss"].data_ptr(), h["correct"].data_ptr())
+        slot.plans[key] = P
+        slot.feat_hw = s
+        return P
+
+    def backward_train_plan(self, slot: Slot, loss_weight: float = 1.0) -> Plan:
+        """Backward of a train-mode forward_plan(slot, True, loss_weight) (whose head launch left dlogits): every
+        parameter gradient into fp.grad, which the plan zeroes first; no image gradient."""
+        key = "bwd.train.%g" % loss_weight
+        if key in slot.plans:
+            return slot.plans[key]
+        if "fwd.train.%g" % loss_weight not in slot.plans:    # the loss weight lives in that forward's dlogits
+            raise ValueError("backward_train_plan(loss_weight=%g) needs forward_plan(slot, True, %g) of the same slot first"
+                             % (loss_weight, loss_weight))
+        P = Plan("vgg." + key)
+        fp, n = self.fp, slot.N
+        h = self.head_bufs(slot)
+        G = lambda name, like: slot.buf("g." + name, like.shape)
+        P.add("zero_grad", _zero_grad_call, fp)
+        feat = slot.bufs["l%d.p" % (len(self.layers) - 1)]
+        d_cur = G("feat", feat)
+        P.hold(h, feat, d_cur)
+        P.add("head_bwd", lib.combat_flat_head_bwd, feat.data_ptr(), n, slot.feat_hw, feat.shape[-1], self.lin_w.data_ptr(),
+              self.classes, h["dlogits"].data_ptr(), d_cur.data_ptr(), fp.grad_phys("classifier.weight").data_ptr(),
+              fp.grad_phys("classifier.bias").data_ptr())
+        bnk = lambda bn: dict(gamma=bn.gamma, dgamma=fp.grad_phys(bn.prefix + ".weight"), dbeta=fp.grad_phys(bn.prefix + ".bias"))
+        for l1 in range(len(self.layers) - 1, 0, -2):
+            l0 = l1 - 1
+            e0, e1 = self.layers[l0], self.layers[l1]
+            y0, a0, y1, a1 = (slot.bufs["l%d.%s" % (l, t)] for l in (l0, l1) for t in ("y", "a"))
+            st0, st1 = slot.norm[e0.bn.prefix], slot.norm[e1.bn.prefix]
+            # through the pool and the second layer's ReLU, then its BatchNorm (sums taken from the tensors)
+            dz1 = G("l%d.dz" % l1, y1)
+            P.hold(a1, d_cur, dz1)
+            P.add("l%d.pool_bwd" % l1, lib.combat_maxpool2_relu_bwd, a1.data_ptr(), d_cur.data_ptr(), n, a1.shape[1],
+                  a1.shape[2], e1.width, dz1.data_ptr())
+            st1.bpending = dict(part=None, rpg=0, **bnk(e1.bn))
+            dy1 = G("l%d.dy" % l1, y1)
+            self._bwd_apply(P, slot, "g." + e1.bn.prefix, dz1, y1, dy1, st1)
+            rec_wgrad(P, "l%d.wgrad" % l1, a0, dy1, e1.pc, fp.grad_phys(e1.prefix + ".weight"))
+            # into the first layer: ReLU mask + BatchNorm sums in the input gradient's epilogue
+            dz0 = G("l%d.dz" % l0, y0)
+            self._dgrad_norm(P, slot, "g." + e0.bn.prefix, dy1, dz0, e1.pc, y0, st0, group_stride=0, slope=0.0, **bnk(e0.bn))
+            dy0 = G("l%d.dy" % l0, y0)
+            self._bwd_apply(P, slot, "g." + e0.bn.prefix, dz0, y0, dy0, st0)
+            src0 = slot.bufs["l%d.p" % (l0 - 1)] if l0 else self.input(slot)
+            rec_wgrad(P, "l%d.wgrad" % l0, src0, dy0, e0.pc, fp.grad_phys(e0.prefix + ".weight"), aux=l0 > 0)
+            if l0:      # to the previous stage's pooled tensor (the first layer has no image gradient)
+                d_cur = G("l%d.dp" % (l0 - 1), src0)
+                rec_conv(P, "l%d.dgrad" % l0, dy0, d_cur, e0.pc, 1)
+                if l0 in (8, 6, 4):   # stages 5 / 4 / 3 complete: their gradient range can travel
+                    P.mark(fp.offsets[e0.prefix + ".weight"][0])
+        P.mark(0)
+        group_wgrads(P, self.device)
+        slot.plans[key] = P
+        return P
+
+    def backward_eval_plan(self, *a, **k):
+        raise NotImplementedError("VGG13 is victim-only on the HIP path: there is no eval-mode input gradient, so it cannot "
+                                  "be the surrogate of a generator step (DESIGN.md section 16)")
+
+
 # --------------------------------------------------------------------------------------------
 # UNet generator
 # --------------------------------------------------------------------------------------------
@@ -1900,7 +2036,7 @@ class FreqEngine(NetEngine):
 # --------------------------------------------------------------------------------------------
 
 ENGINES = {"preact_resnet18": PreActEngine, "resnet18": ResNetEngine, "unet": UnetEngine, "cunet": CUnetEngine,
-           "freq": FreqEngine, "gridgen": GridEngine}
+           "freq": FreqEngine, "gridgen": GridEngine, "vgg": VggEngine}
 
 
 def build_engine(module) -> NetEngine:
@@ -2036,7 +2172,7 @@ def module_forward(module, x: torch.Tensor) -> torch.Tensor:
     params = tuple(module.parameters())
     if module.arch == "unet":
         return _GeneratorFn.apply(module, x, *params)
-    if module.arch in ("preact_resnet18", "resnet18"):
+    if module.arch in ("preact_resnet18", "resnet18", "vgg"):
         return _ClassifierFn.apply(module, x, *params)
     if module.arch == "gridgen":
         return _GridFn.apply(module, x, *params)

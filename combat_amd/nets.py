@@ -13,6 +13,7 @@ Mirrored interfaces:
   PreActResNet18    classifier_models/preact_resnet.py:13-40, 72-110
   ResNet18          classifier_models/resnet.py:15-37, 68-106
   FrequencyModel    defenses/frequency_based/model.py:8-52
+  VGG               classifier_models/vgg.py:7-45
 """
 from __future__ import annotations
 
@@ -197,6 +198,38 @@ class FrequencyModel(_HipModule):
         self.linear6 = nn.Linear(2048 * INPUT_SIZE_TO_SCALER[input_size], num_classes)
 
 
+# Output widths of the 3x3 convolutions, stage by stage; a 2x2 max-pool closes every stage (classifier_models/vgg.py:7-12).
+VGG_STAGES = {
+    "VGG11": ((64,), (128,), (256, 256), (512, 512), (512, 512)),
+    "VGG13": ((64, 64), (128, 128), (256, 256), (512, 512), (512, 512)),
+    "VGG16": ((64, 64), (128, 128), (256, 256, 256), (512, 512, 512), (512, 512, 512)),
+    "VGG19": ((64, 64), (128, 128), (256, 256, 256, 256), (512, 512, 512, 512), (512, 512, 512, 512)),
+}
+VGG_INPUT_SIZE_TO_SCALER = {32: 1, 64: 4}   # the reference's table (vgg.py:15): five pools leave 1 x 1 or 2 x 2 x 512
+
+
+class VGG(_HipModule):
+    """classifier_models/vgg.py:18-45.  `features` keeps the reference's indices (conv, BatchNorm, ReLU per layer, the
+    parameter-less pools and the closing AvgPool2d(1, 1) included), so the state-dict keys are features.<i>.* and
+    classifier.*, in the reference's construction order.  Only "VGG13" has an engine (combat_amd.engine.VggEngine)."""
+
+    arch = "vgg"
+
+    def __init__(self, vgg_name, num_classes=10, n_input=3, input_size=32):
+        super().__init__()
+        self.vgg_name, self.num_classes, self.n_input, self.input_size = vgg_name, num_classes, n_input, input_size
+        scaler = VGG_INPUT_SIZE_TO_SCALER[input_size]
+        mods, cin = [], n_input
+        for stage in VGG_STAGES[vgg_name]:
+            for width in stage:
+                mods += [nn.Conv2d(cin, width, kernel_size=3, padding=1), nn.BatchNorm2d(width), nn.ReLU(inplace=True)]
+                cin = width
+            mods.append(nn.MaxPool2d(kernel_size=2, stride=2))
+        mods.append(nn.AvgPool2d(kernel_size=1, stride=1))
+        self.features = nn.Sequential(*mods)
+        self.classifier = nn.Linear(512 * scaler, num_classes)
+
+
 def configure_dataset(opt) -> None:
     """Input dimensions / class count per dataset, as every entry script's main() sets them
     (train_generator.py:470-486; imagenet10: train_generator_wanet.py:472-477 -- 224 x 224, 10 classes, bs 32)."""
@@ -225,3 +258,21 @@ def default_classifier(opt):
     if opt.dataset == "imagenet10":   # train_generator_wanet.py:72-74 (the reference's scaler table lacks 224: SURVEY D4)
         return ResNet18(num_classes=opt.num_classes, input_size=opt.input_height)
     raise Exception("Invalid Dataset")
+
+
+ZOO = ("default", "vgg13")   # the `--model` values with an engine; the reference's table also names mobilenetv2, vit, simplevitsmall8
+
+
+def classifier_for(opt):
+    """The victim of `--model` (train_victim.py:23-28, :82-85; eval.py:100-103; train_clean_classifier.py:63-66):
+    `default` -> default_classifier(opt); `vgg13` -> VGG("VGG13") for cifar10 / celeba.  The generator scripts keep
+    default_classifier: VGG13 is a victim here, not a surrogate."""
+    model = getattr(opt, "model", "default")
+    if model == "default":
+        return default_classifier(opt)
+    if model == "vgg13":
+        if opt.dataset not in ("cifar10", "celeba"):
+            raise Exception("--model vgg13 runs on cifar10 and celeba only: the reference's VGG has no head for %d x %d inputs"
+                            " (its input_size2scaler table lacks the size)" % (opt.input_height, opt.input_height))
+        return VGG("VGG13", num_classes=opt.num_classes, n_input=opt.input_channel, input_size=opt.input_height)
+    raise Exception("--model %s has no engine on the HIP path; available: %s" % (model, ", ".join(ZOO)))

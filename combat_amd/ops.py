@@ -572,6 +572,28 @@ def maxpool2(x, out) -> None:
     check(lib.combat_maxpool2(x.data_ptr(), n, h, w, c, out.data_ptr(), _stream()), "combat_maxpool2")
 
 
+def maxpool2_relu_bwd(a, d_pooled, d_a) -> None:
+    """d_a = gradient at the post-ReLU tensor `a` that combat_maxpool2 pooled (first-maximum ties, ReLU mask)."""
+    n, h, w, c = a.shape
+    assert tuple(d_pooled.shape) == (n, h // 2, w // 2, c) and tuple(d_a.shape) == tuple(a.shape)
+    check(lib.combat_maxpool2_relu_bwd(a.data_ptr(), d_pooled.data_ptr(), n, h, w, c, d_a.data_ptr(), _stream()),
+          "combat_maxpool2_relu_bwd", "a=%s" % (tuple(a.shape),))
+
+
+def flat_head_fwd(feat, weight, bias, logits, targets=None, loss_weight=1.0, dlogits=None, loss=None, correct=None) -> None:
+    n, hw, _, c = feat.shape
+    check(lib.combat_flat_head_fwd(feat.data_ptr(), n, hw, c, weight.data_ptr(), bias.data_ptr(), weight.shape[0],
+                                   _p(targets), float(loss_weight), logits.data_ptr(), _p(dlogits), _p(loss), _p(correct),
+                                   _stream()), "combat_flat_head_fwd", "feat=%s" % (tuple(feat.shape),))
+
+
+def flat_head_bwd(feat, weight, dlogits, d_feat=None, dw=None, db=None) -> None:
+    n, hw, _, c = feat.shape
+    check(lib.combat_flat_head_bwd(feat.data_ptr(), n, hw, c, weight.data_ptr(), weight.shape[0], dlogits.data_ptr(),
+                                   _p(d_feat), _p(dw), _p(db), _stream()), "combat_flat_head_bwd",
+          "feat=%s" % (tuple(feat.shape),))
+
+
 def elu_affine(x, scale, shift, out) -> None:
     c = x.shape[-1]
     check(lib.combat_elu_affine(x.data_ptr(), x.numel() // c, c, scale.data_ptr(), shift.data_ptr(), out.data_ptr(),

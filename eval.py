@@ -11,12 +11,12 @@ from combat_amd import api
 from combat_amd import dist as cdist
 from combat_amd.data import get_dataloader
 from combat_amd.log import SummaryWriter, progress_bar
-from combat_amd.nets import GridGenerator, UnetGenerator, configure_dataset, default_classifier
+from combat_amd.nets import GridGenerator, UnetGenerator, configure_dataset, classifier_for
 from combat_amd.step import create_targets_bd
 
 
 def get_model(opt):
-    return default_classifier(opt).to(opt.device), UnetGenerator(opt).to(opt.device)
+    return classifier_for(opt).to(opt.device), UnetGenerator(opt).to(opt.device)
 
 
 def eval(netC, netG, test_dl, tf_writer, opt):

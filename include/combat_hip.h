@@ -800,6 +800,34 @@ int combat_dct_u8(const float *x, const float *D, int32_t n, int32_t hw, void *o
 int combat_linear_nhwc(const void *x, int32_t n, int32_t h, int32_t w, int32_t C, const float *W, const float *b,
                        int32_t classes, float *logits, void *stream);
 
+/* ---- VGG victim classifier (classifier_models/vgg.py): the two pieces its conv -> BatchNorm -> ReLU chain lacks.
+ *
+ * combat_maxpool2_relu_bwd: backward of nn.ReLU(inplace=True) -> nn.MaxPool2d(2, 2) (vgg.py:36 after :41) in one pass.
+ * a bf16 [n][h][w][C] = the post-ReLU tensor the forward pooled (combat_maxpool2's input), d_pooled bf16
+ * [n][h/2][w/2][C], d_a bf16 [n][h][w][C] (every element written once: no zero fill, no atomics).  Per window and channel
+ * the pooled gradient goes to the FIRST maximum in the order (dy, dx) = (0,0), (0,1), (1,0), (1,1) (MaxPool2d's strict `>`
+ * scan; bf16 activations tie often) if that maximum is > 0, and the other three elements -- all four of a window whose
+ * maximum is <= 0, where the ReLU's gradient is 0 -- get 0.  COMBAT_EINVAL for a NULL pointer, n, h, w, C < 1, odd h or
+ * w, C & 7. */
+int combat_maxpool2_relu_bwd(const void *a, const void *d_pooled, int32_t n, int32_t h, int32_t w, int32_t C, void *d_a,
+                             void *stream);
+/* combat_flat_head_fwd: out.view(n, -1) -> nn.Linear -> nn.CrossEntropyLoss (vgg.py:25-29; the AvgPool2d(1, 1) of :44 is
+ * the identity) over feat bf16 [n][hw][hw][C], hw in {1, 2}, C * hw * hw <= 2048.  W fp32 [classes][C*hw*hw] as torch stores
+ * it: the column of feature (y, x, c) is the NCHW flatten c*hw*hw + y*hw + x.  logits fp32 [n][classes].  With targets
+ * (int64 [n]): *loss_sum += loss_weight / n * sum_i CE_i, *correct += #(first maximal class == target), dlogits fp32
+ * [n][classes] = loss_weight / n * (softmax - onehot) -- the accumulator semantics of combat_head_fwd (deterministic mode:
+ * the images' shares in index order); each of the three may be NULL.  targets NULL: logits only (the three must be NULL).
+ * combat_flat_head_bwd: from dlogits, d_feat bf16 [n][hw][hw][C] = dlogits W (may be NULL) and dW fp32 [classes][C*hw*hw],
+ * db fp32 [classes] (both or neither; OVERWRITTEN, not accumulated): sums over the images in index order by one thread per
+ * element in EVERY mode, no atomics.  feat is read for dW only.
+ * Both: COMBAT_EINVAL for hw outside {1, 2}, C < 8 or C & 7, C*hw*hw > 2048, classes outside 1..16, n < 1, a NULL feat (bwd:
+ * with dW) / W / b / logits / dlogits (bwd), nothing to compute (bwd: d_feat and dW both NULL). */
+int combat_flat_head_fwd(const void *feat, int32_t n, int32_t hw, int32_t C, const float *W, const float *b,
+                         int32_t classes, const int64_t *targets, float loss_weight, float *logits, float *dlogits,
+                         float *loss_sum, int32_t *correct, void *stream);
+int combat_flat_head_bwd(const void *feat, int32_t n, int32_t hw, int32_t C, const float *W, int32_t classes,
+                         const float *dlogits, void *d_feat, float *dW, float *db, void *stream);
+
 /* ---- WaNet trigger (train_generator_wanet.py:151-157, 196-202, 212; GridGenerator networks/models.py:344-385).
  * The reference's GridGenerator pools an affine-free InstanceNorm output (spatial mean exactly 0), so its output is
  * tanh(fc2(lrelu(fc1.bias))) for every input: a constant [2][S][S] field (tests/test_oracle_golden.py pins this

@@ -33,5 +33,7 @@ print("train_generator.py: %.2f s per epoch of 200 train + 200 eval batches of 1
 print(epochs(out))
 _, out = run("train_victim.py", "--synthetic_size", "25600", "--saving_prefix", "victim", "--load_checkpoint", "g3_clean", "--n_iters", "3")
 print("train_victim.py:\n" + epochs(out))
+_, out = run("train_victim.py", "--model", "vgg13", "--synthetic_size", "25600", "--saving_prefix", "victim_vgg13", "--load_checkpoint", "g3_clean", "--n_iters", "3")
+print("train_victim.py --model vgg13:\n" + epochs(out))
 _, out = run("train_generator_wanet.py", "--synthetic_size", "25600", "--saving_prefix", "w3", "--load_checkpoint_clean", "classifier_clean", "--n_iters", "2")
 print("train_generator_wanet.py:\n" + epochs(out))

@@ -8,12 +8,12 @@ import torch
 from combat_amd import api, dist as cdist, run
 from combat_amd.data import get_dataloader
 from combat_amd.log import progress_bar
-from combat_amd.nets import default_classifier
+from combat_amd.nets import classifier_for
 from combat_amd.step import ClassifierStep
 
 
 def get_model(opt):
-    netC = default_classifier(opt).to(opt.device)
+    netC = classifier_for(opt).to(opt.device)
     optimizerC = torch.optim.SGD(netC.parameters(), opt.lr_clean, momentum=0.9, weight_decay=5e-4, nesterov=True)
     schedulerC = torch.optim.lr_scheduler.MultiStepLR(optimizerC, opt.scheduler_clean_milestones, opt.scheduler_clean_lambda)
     return netC, optimizerC, schedulerC

@@ -7,12 +7,12 @@ import torch
 from combat_amd import api, dist as cdist, run
 from combat_amd.data import get_dataloader
 from combat_amd.log import image_grid, progress_bar
-from combat_amd.nets import UnetGenerator, default_classifier
+from combat_amd.nets import UnetGenerator, classifier_for
 from combat_amd.step import ClassifierStep, create_targets_bd
 
 
 def get_model(opt):
-    netC = default_classifier(opt).to(opt.device)
+    netC = classifier_for(opt).to(opt.device)
     netG = UnetGenerator(opt).to(opt.device)
     optimizerC = torch.optim.SGD(netC.parameters(), opt.lr_C, momentum=0.9, weight_decay=5e-4, nesterov=True)
     schedulerC = torch.optim.lr_scheduler.MultiStepLR(optimizerC, opt.schedulerC_milestones, opt.schedulerC_lambda)
